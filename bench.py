@@ -13,9 +13,12 @@ trigger; every 128th step runs the burst (exact H2O selection + slot-table compa
 28 layers).  K steps are timed between barriers; `value` = tokens of all GPUs / max-over-ranks
 time.  The model's dense layers are outside this build (hot path only).
 
-One JSON line is printed by rank 0.  `roofline` times every stage-1 launch of the timed
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times the K steps and prints
+the line.  `--full` adds the side legs to it: `roofline` times every stage-1 launch of the timed
 region with HIP events on the launch stream; `cpu_baseline` times the numpy oracle on a
-bounded sample of the same workload on the host (rank 0, N=1 only).
+bounded sample of the same workload on the host (rank 0, N=1 only); `burst`, `paths` and `e2e`
+are described in DESIGN.md section 5.  `--dump-outputs DIR` writes what the last timed step
+computed as DIR/<name>.npy.
 """
 
 from __future__ import annotations
@@ -43,6 +46,13 @@ def parse():
     ap.add_argument("--batch", type=int, default=256, help="sequences per GPU (a 288 GB MI355X holds far more 4224-token "
                     "rows than this; 256 rows = one unsplit stage-1 workgroup per CU; "
                     "64 = the round-1 default, see profiles/ for 64 / 128 / 512)")
+    ap.add_argument("--full", action="store_true", help="also run the side legs: CPU baseline, the burst on its own, the "
+                    "roofline leg, the other configurations and the end-to-end leg (each has its --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (float32 / float64): "
+                         "the attention outputs and the cumulative H2O scores of a fixed sample of sequences, all layers, "
+                         "and every row's length; rank 0 only.  Every step of the run then copies its attention outputs into "
+                         "a buffer of the caller's, as `step(..., outputs=)` does for any caller that wants them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-events", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of hipGraph replay")
@@ -261,6 +271,32 @@ def _traffic_in_child(batch: int, timeout_s: int = 150) -> dict:
             "measured_in": "children of this bench.py run"}
 
 
+def dump_outputs(out_dir: str, drv, outs: torch.Tensor, n_attn: int = 64, n_score: int = 32) -> None:
+    """`--dump-outputs`: what a caller of `drv.step(q, k, v, outs)` holds after the last timed step, as float32 / float64
+    .npy files.  The whole arrays are 100 MB and more at the default batch, so a fixed, seeded sample of the sequences is
+    written (41 MB at the default shapes, all layers):
+      attn_out.npy    [layers, n_attn, q heads, head_dim]  the step's attention outputs
+      h2o_scores.npy  [layers, n_score, longest row]       cumulative H2O scores of the rows' resident tokens, 0 beyond a row
+      row_len.npy     [B]                                  resident tokens of every sequence's row
+    The sample is the head of one seeded permutation of the B sequences: n_attn of them, the first n_score with scores."""
+    cm = drv.cache_manager
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    B = len(drv.seqs)
+    pick = np.random.default_rng(20260625).permutation(B)[: min(B, n_attn)]
+    row_len = drv.row_len()
+    layers = list(cm.kv_transformer_layer_indices())
+    scored = pick[: min(B, n_score)]
+    scores = np.zeros((len(layers), len(scored), int(row_len[scored].max())), dtype=np.float32)
+    for i, layer_idx in enumerate(layers):
+        for j, b in enumerate(scored):
+            s = cm.h2o_score(layer_idx, drv.seqs[int(b)].seq_id).float().cpu().numpy()
+            scores[i, j, : s.shape[0]] = s
+    np.save(os.path.join(out_dir, "attn_out.npy"), outs[:, torch.from_numpy(pick).to(outs.device)].float().cpu().numpy())
+    np.save(os.path.join(out_dir, "h2o_scores.npy"), scores)
+    np.save(os.path.join(out_dir, "row_len.npy"), row_len.astype(np.float64))
+
+
 def _e2e_in_child(args, world: int, rank: int, local_rank: int, timeout_s: int = 200) -> list[dict]:
     """The end-to-end leg (tools/e2e_decoder.py) in a CHILD process per rank, after this process has released its GPU
     memory: a random-weight Qwen2.5-7B-shaped decoder (torch dense layers) around this build's attention path.  One GPU:
@@ -332,8 +368,11 @@ def main():
                 print(json.dumps(line), flush=True)
         return
     stub = bool(args.stub_driver)
-    if stub:
-        args.no_cpu_baseline = args.no_kernel_events = args.no_paths = True
+    if stub and args.dump_outputs:
+        print("[bench] --dump-outputs needs the real driver, not --stub-driver", file=sys.stderr)
+        sys.exit(2)
+    if stub or not args.full:
+        args.no_cpu_baseline = args.no_kernel_events = args.no_paths = args.no_e2e = True
     if use_dist:
         import torch.distributed as dist
         if stub:
@@ -367,6 +406,8 @@ def main():
     cm.permute_free_slots(20260625 + rank)
     drv.admit_resident_rows(B, budget, logical_len=131072, seed=20260625 + rank, device_rng=True)
     q, k, v = drv.random_step_inputs(seed=7 + rank)
+    dump = bool(args.dump_outputs) and rank == 0
+    outs = torch.zeros_like(q) if dump else None       # [layers, B, q heads, head_dim]: every step's attention outputs
 
     # ---- stage-1 launch timing with HIP events on the launch stream (torch's current stream).
     # Eager mode: the arguments of every stage-1 launch of a step are captured, and right after the
@@ -417,28 +458,30 @@ def main():
     # object load of the selection / compaction kernels, first-use allocations: ~45 ms) are not billed to the K timed
     # steps.  The timed region still contains its bursts (one per 128 steps per sequence) at steady-state cost.
     for _ in range(int(conf.h2o_decode_eviction_interval) + 2):
-        drv.step(q, k, v)
+        drv.step(q, k, v, outs)
     warmup = max(args.warmup, 2 if not args.no_graph else 0)   # graph capture happens in the first steps
     for _ in range(warmup):
-        drv.step(q, k, v)
+        drv.step(q, k, v, outs)
     barrier()
     bursts0 = int(cm._h2o_counters["decode_eviction_bursts"])
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        drv.step(q, k, v)
+        drv.step(q, k, v, outs)
     barrier()
     elapsed = time.perf_counter() - t0
     bursts_in_window = (int(cm._h2o_counters["decode_eviction_bursts"]) - bursts0) // B
+    if dump:
+        dump_outputs(args.dump_outputs, drv, outs)
     # ---- the burst on its own: run on to the next eviction step, time the plain steps before it and the step that carries
     # the burst (select + compact over all 28 layers x B rows); every sequence pays it once per `interval` steps
     burst = None
-    if not args.no_graph and not stub:
+    if args.full and not args.no_graph and not stub:
         plain = []
         for _ in range(2 * interval + 2):
             n0 = int(cm._h2o_counters["decode_eviction_bursts"])
             torch.cuda.synchronize()
             ts = time.perf_counter()
-            drv.step(q, k, v)
+            drv.step(q, k, v, outs)
             torch.cuda.synchronize()
             dt = (time.perf_counter() - ts) * 1e3
             if int(cm._h2o_counters["decode_eviction_bursts"]) > n0:
@@ -455,7 +498,7 @@ def main():
 
         for _ in range(args.event_steps):
             record["on"] = True
-            drv.step(q, k, v, after_layers=after_layers)
+            drv.step(q, k, v, outs, after_layers=after_layers)
     from sparse_vllm_amd.replicas import aggregate_throughput, gather_per_rank
     per_rank_s = gather_per_rank(elapsed, device=device)          # every replica's own clock (N = 1: one entry)
     tokens, elapsed = aggregate_throughput(B * args.steps, elapsed, device=device)

@@ -14,9 +14,9 @@ stats() {  # stats <name> <cmd...>: kernel-trace stats csv of one command
   local f; f=$(find "$O/_prof_$tag" -type f -name '*kernel_stats.csv' | head -1)
   [ -n "$f" ] && cp "$f" "$O/$name" || echo "no stats for $name" >&2
 }
-# headline bench: plain run (the judged line) and the same command under the profiler
-timeout 600 python3 "$R/bench.py" < /dev/null > "$O/bench_stdout.log" 2> "$O/bench_stderr.log"; tail -1 "$O/bench_stdout.log" > "$O/bench_line.json"
-stats bench_kernel_stats.csv python3 "$R/bench.py" --steps 128 --warmup 8 --no-cpu-baseline --no-paths --no-e2e     # (the other configurations launch the same kernels at other shapes: they would pollute the per-kernel averages)
+# headline bench with every side leg (--full), and the same workload under the profiler
+timeout 600 python3 "$R/bench.py" --full < /dev/null > "$O/bench_stdout.log" 2> "$O/bench_stderr.log"; tail -1 "$O/bench_stdout.log" > "$O/bench_line.json"
+stats bench_kernel_stats.csv python3 "$R/bench.py" --full --steps 128 --warmup 8 --no-cpu-baseline --no-paths --no-e2e     # (the other configurations launch the same kernels at other shapes: they would pollute the per-kernel averages)
 grep '^{' "$O/_bench_kernel_stats.log" | tail -1 > "$O/bench_line_profiled.json"
 json_line() {  # json_line <file> <cmd...>: the command's last stdout line appended to <file>, one retry if it printed none
   local f=$1; shift
@@ -28,9 +28,9 @@ json_line() {  # json_line <file> <cmd...>: the command's last stdout line appen
   done
   echo "$out" >> "$f"
 }
-for b in 1 8 32; do json_line "$O/bench_small_batches.jsonl" python3 "$R/bench.py" --batch $b --no-cpu-baseline --no-kernel-events --no-e2e; done
+for b in 1 8 32; do json_line "$O/bench_small_batches.jsonl" python3 "$R/bench.py" --full --batch $b --no-cpu-baseline --no-kernel-events --no-e2e; done
 # the roofline leg at the neighbouring batch sizes (the default is 256)
-for b in 64 128 512; do json_line "$O/bench_other_batches.jsonl" python3 "$R/bench.py" --batch $b --no-cpu-baseline --no-e2e --no-paths; done
+for b in 64 128 512; do json_line "$O/bench_other_batches.jsonl" python3 "$R/bench.py" --full --batch $b --no-cpu-baseline --no-e2e --no-paths; done
 # other configurations
 timeout 600 python3 "$R/tools/pathbench.py" --graph < /dev/null 2>/dev/null | grep '^{' > "$O/paths/pathbench_graph.jsonl"
 timeout 600 python3 "$R/tools/pathbench.py" < /dev/null 2>/dev/null | grep '^{' > "$O/paths/pathbench_eager.jsonl"
