@@ -40,7 +40,7 @@ typedef enum SvkStatus {
   SVK_ERR_LAUNCH = -4   /* HIP launch failure                  -> RuntimeError   */
 } SvkStatus;
 
-#define SVK_ABI_VERSION 20
+#define SVK_ABI_VERSION 21
 
 int svk_abi_version(void);
 const char* svk_last_error(void);
@@ -473,6 +473,68 @@ int32_t svk_prefill_score_window_pad(int32_t num_q_heads, int32_t num_kv_heads, 
 int64_t svk_prefill_score_workspace_bytes(int32_t n_ranges, int32_t num_q_heads, int32_t num_kv_heads,
                                           int32_t max_query_len, int32_t score_cols);
 int svk_prefill_score(const SvkPrefillScoreArgs* a, svk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * R-KV: redundancy scores and joint retention scores
+ * ---------------------------------------------------------------------------------- */
+
+/* redundancy[row, :] for the `n` tokens slots[row, 0..n) of every row (oldest first), one layer:
+ *   f_i      = key i flattened over the KV heads (Hkv*D values), f32, divided by max(|f_i|_2, 1e-6)
+ *   sim[i,j] = f_i . f_j, sim[i,i] = 0;  threshold > 0: entries below it are set to 0
+ *   keep > 0 and n > 1: for every i, the `keep` most recent j > i with sim[i,j] > 0 are set to 0
+ *   avg[i]   = sum_j sim[i,j] / n;  redundancy = softmax(avg) over the n tokens (n = 1: [1.0])
+ * Replaces RKVCacheManager.redundancy_scores_from_keys{,_batch}, engine/cache_manager/rkv.py:617-697 (the arithmetic is
+ * :634-654), which materialises the [n, n] similarity, two masks and a cumulative sum in torch; the slots take the place
+ * of materialize_attention_keys (:746-749, :821-824).  bf16 MFMA with f32 accumulation, the norms applied to the
+ * accumulator; no [n, n] array, no float atomics, the result does not depend on the slot order.
+ * `redundancy` may be NULL: the averages alone are left in the workspace for svk_rkv_joint_scores (rows of
+ * svk_rkv_redundancy_avg_stride(n) floats from the start of `workspace`). */
+typedef struct SvkRkvRedundancyArgs {
+  const uint16_t* k_cache;      /* [slots, Hkv, D] bf16, heads contiguous inside a slot, 16-byte aligned   */
+  const int32_t* slots;         /* [rows, slot_stride]: slot of candidate token c of the row, any order    */
+  float* redundancy;            /* NULL or [rows, redundancy_stride] f32 out                               */
+  float* workspace;             /* >= svk_rkv_redundancy_workspace_bytes(rows, n), 16-byte aligned         */
+  int64_t workspace_bytes;
+  int64_t kv_slot_stride;       /* elements between slots (>= Hkv*D, multiple of 8)                        */
+  int64_t kv_num_slots;         /* slots in k_cache: table entries are clamped into the pool               */
+  int64_t slot_stride;
+  int64_t redundancy_stride;
+  int32_t rows;                 /* <= 65535                                                                */
+  int32_t n;                    /* tokens per row, <= max_tokens                                           */
+  int32_t num_kv_heads;         /* 1, 2, 4 or 8                                                            */
+  int32_t head_dim;             /* 128                                                                     */
+  int32_t recent_similar_keep;  /* >= 0 (config rkv_recent_similar_keep)                                   */
+  int32_t max_tokens;           /* config rkv_max_redundancy_tokens: n above it is SVK_ERR_STATE (:627-632) */
+  float similarity_threshold;   /* [0, 1] (config rkv_similarity_threshold); 0 = nothing is cut            */
+  int32_t _pad;
+} SvkRkvRedundancyArgs;
+int64_t svk_rkv_redundancy_workspace_bytes(int32_t rows, int32_t n);
+int64_t svk_rkv_redundancy_avg_stride(int32_t n);
+int svk_rkv_redundancy(const SvkRkvRedundancyArgs* a, svk_stream_t stream);
+
+/* Joint retention score of the candidates [candidate_start, candidate_start + n_candidates) of every row:
+ *   red      = softmax(avg[row, 0..window))
+ *   final[c] = importance[row, candidate_start + c]                                  c <  n_candidates - window
+ *            = alpha * importance[...] - (1 - alpha) * red[c - (n_candidates - window)]   on the last `window` candidates
+ *   scores[row, candidate_start + c] = final[c]   (the row layout svk_select_prefix_topk_suffix reads with
+ *   prefix = candidate_start; columns outside the candidates are not written and not read by that selection)
+ * Replaces RKVCacheManager.joint_retention_scores and the score assembly of select_rkv_indices{,_batch},
+ * engine/cache_manager/rkv.py:700-708, :739-760, :815-835.  `avg` is the workspace of svk_rkv_redundancy.
+ * `scores` NULL: only `redundancy` (NULL or [rows, redundancy_stride], the softmax itself) is written. */
+typedef struct SvkRkvJointScoreArgs {
+  const float* avg;             /* [rows, avg_stride] f32 (window > 0)                                     */
+  const float* importance;      /* [rows, importance_stride] f32, indexed by cache position                */
+  float* scores;                /* NULL or [rows, score_stride] f32 out, indexed by cache position         */
+  float* redundancy;            /* NULL or [rows, redundancy_stride] f32 out                               */
+  int64_t avg_stride, importance_stride, score_stride, redundancy_stride;
+  int32_t rows;
+  int32_t window;               /* tokens svk_rkv_redundancy scored (0 <= window <= n_candidates)          */
+  int32_t n_candidates;
+  int32_t candidate_start;      /* = number of sink tokens                                                 */
+  float alpha;                  /* [0, 1] (config rkv_alpha)                                               */
+  int32_t _pad;
+} SvkRkvJointScoreArgs;
+int svk_rkv_joint_scores(const SvkRkvJointScoreArgs* a, svk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Quest: query-aware page top-k

@@ -23,7 +23,7 @@ SVK_SCORE_NONE = 0
 SVK_SCORE_HEADMAX = 2
 SVK_SCORE_PERHEAD = 3
 
-SVK_ABI_VERSION = 20
+SVK_ABI_VERSION = 21
 
 SVK_PREFILL_SCORE_PROBABILITY = 0
 SVK_PREFILL_SCORE_LOGITS = 1
@@ -315,6 +315,19 @@ class SvkKiviDecodeStage1Args(C.Structure):
                [("new_k", _p), ("new_v", _p), ("new_slots", _p), ("new_stride_b", _i64), ("new_stride_h", _i64)]
 
 
+class SvkRkvRedundancyArgs(C.Structure):
+    _fields_ = [("k_cache", _p), ("slots", _p), ("redundancy", _p), ("workspace", _p)] + \
+               [(n, _i64) for n in ("workspace_bytes", "kv_slot_stride", "kv_num_slots", "slot_stride", "redundancy_stride")] + \
+               [(n, _i32) for n in ("rows", "n", "num_kv_heads", "head_dim", "recent_similar_keep", "max_tokens")] + \
+               [("similarity_threshold", _f32), ("_pad", _i32)]
+
+
+class SvkRkvJointScoreArgs(C.Structure):
+    _fields_ = [("avg", _p), ("importance", _p), ("scores", _p), ("redundancy", _p)] + \
+               [(n, _i64) for n in ("avg_stride", "importance_stride", "score_stride", "redundancy_stride")] + \
+               [(n, _i32) for n in ("rows", "window", "n_candidates", "candidate_start")] + [("alpha", _f32), ("_pad", _i32)]
+
+
 # symbol -> (argtypes) ; every entry point declared in include/svk.h
 ENTRY_POINTS = {
     "svk_abi_version": ([], C.c_int),
@@ -338,6 +351,10 @@ ENTRY_POINTS = {
     "svk_prefill_score_workspace_bytes": ([_i32, _i32, _i32, _i32, _i32], C.c_int64),
     "svk_prefill_score_window_pad": ([_i32, _i32, _i32], C.c_int32),
     "svk_prefill_score": ([C.POINTER(SvkPrefillScoreArgs), _p], C.c_int),
+    "svk_rkv_redundancy_workspace_bytes": ([_i32, _i32], C.c_int64),
+    "svk_rkv_redundancy_avg_stride": ([_i32], C.c_int64),
+    "svk_rkv_redundancy": ([C.POINTER(SvkRkvRedundancyArgs), _p], C.c_int),
+    "svk_rkv_joint_scores": ([C.POINTER(SvkRkvJointScoreArgs), _p], C.c_int),
     "svk_deltakv_decode_alloc": ([C.POINTER(SvkDeltakvDecodeAllocArgs), _p], C.c_int),
     "svk_deltakv_device_step_begin": ([C.POINTER(SvkDeltakvDeviceStepArgs), _p], C.c_int),
     "svk_deltakv_static_decode_plan": ([C.POINTER(SvkDeltakvPlanArgs), _p], C.c_int),

@@ -4,3 +4,4 @@
 from .gqa_flash_decoding_stage1 import flash_decode_stage1, flash_decode_stage1_with_score  # noqa: F401
 from .flash_decoding_stage2 import flash_decode_stage2  # noqa: F401
 from .store_kvcache import store_kvcache  # noqa: F401
+from .rkv_ops import redundancy_scores_from_slots, select_rkv_indices_batch  # noqa: F401

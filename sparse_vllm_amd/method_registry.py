@@ -5,6 +5,8 @@ canonical names :37-48, policy table :211-237, `normalize_sparse_method` :240-24
 policy resolution :317-348) so that `sparse_method=` strings written for the reference
 select the same method here.  Methods outside this build's scope (SURVEY.md section 8:
 omnikv, rkv, skipkv, pyramidkv) are *known names* that `CacheManager.create` refuses.
+R-KV's scoring kernels exist (`kernels/rkv_ops.py`: redundancy scores and the joint selection);
+its cache manager does not, so `rkv` is still refused.
 """
 
 from __future__ import annotations
