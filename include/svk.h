@@ -40,7 +40,7 @@ typedef enum SvkStatus {
   SVK_ERR_LAUNCH = -4   /* HIP launch failure                  -> RuntimeError   */
 } SvkStatus;
 
-#define SVK_ABI_VERSION 21
+#define SVK_ABI_VERSION 22
 
 int svk_abi_version(void);
 const char* svk_last_error(void);
@@ -535,6 +535,84 @@ typedef struct SvkRkvJointScoreArgs {
   int32_t _pad;
 } SvkRkvJointScoreArgs;
 int svk_rkv_joint_scores(const SvkRkvJointScoreArgs* a, svk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * MLA: split-KV decode attention over the latent cache, with fused token scores
+ * ---------------------------------------------------------------------------------- */
+
+/* Stage 1 of multi-head latent attention decode.  A token owns one latent row (512 bf16) and one RoPE row (64 bf16)
+ * shared by all query heads.  Per batch lane b and block of `block_seq` positions, with
+ * slot_t = active_slots[request_indices[b], t] for t < min(context_lens[b], max_context_len):
+ *   S[h, t]  = q_latent[b,h,:] . latent[slot_t,:] + q_rope[b,h,:] . rope[slot_t,:]     bf16 operands, f32 accumulate
+ *   attn_score <- raw S (before softmax_scale), see score_mode
+ *   online softmax of S * softmax_scale over the block, P rounded to bf16 before P . latent
+ *   mid_o[b,h,blk,:] = acc / sum_exp (512 f32),  mid_lse[b,h,blk] = max + log(sum_exp);  a block without tokens: (0, -inf)
+ * A slot outside [0, num_slots) is masked out: no row is read, it contributes nothing, its score entry is not written.
+ * A lane whose request index lies outside [0, slot_rows) has length 0.
+ * Scores (plain stores, no atomics): SVK_SCORE_HEADMAX [B, W] = max over the heads, every valid position below the
+ * length written exactly once per launch; SVK_SCORE_PERHEAD [B, H, W]; positions at or beyond the length are left alone.
+ * The cache is two pointers with their slot strides: the reference's two tensors ([slots,1,512], [slots,1,64]) or one
+ * interleaved [slots, 576] allocation (rope_cache = latent_cache + 512, both strides 576).
+ * Replaces kernels/triton/mla/decode_stage1.py:141-255 (launch checks :325-436). */
+typedef struct SvkMlaDecodeStage1Args {
+  const uint16_t* q_latent;      /* [B, H, 512] bf16, 16-byte aligned rows                                  */
+  const uint16_t* q_rope;        /* [B, H, 64] bf16, 16-byte aligned rows                                   */
+  const uint16_t* latent_cache;  /* bf16, 16-byte aligned                                                   */
+  const uint16_t* rope_cache;    /* bf16, 16-byte aligned                                                   */
+  const int32_t* active_slots;   /* [slot_rows, slots_stride]                                               */
+  const int32_t* request_indices;/* [B]                                                                     */
+  const int32_t* context_lens;   /* [B]                                                                     */
+  float* mid_o;                  /* [B, H, nblk, 512] f32 out, nblk = ceil(max_context_len / block_seq)     */
+  float* mid_lse;                /* [B, H, nblk] f32 out (block stride 1)                                   */
+  float* attn_score;             /* NULL or f32 out, see score_mode                                         */
+  int64_t q_latent_stride_b, q_latent_stride_h, q_rope_stride_b, q_rope_stride_h;   /* elements, multiples of 8 */
+  int64_t latent_slot_stride;    /* elements between slots (>= 512, multiple of 8)                          */
+  int64_t rope_slot_stride;      /* elements between slots (>= 64, multiple of 8)                           */
+  int64_t num_slots;             /* slots in the pool                                                       */
+  int64_t slots_stride;          /* >= max_context_len                                                      */
+  int64_t mid_o_stride_b, mid_o_stride_h, mid_o_stride_s;      /* elements, multiples of 4                  */
+  int64_t mid_lse_stride_b, mid_lse_stride_h;
+  int64_t score_stride_b, score_stride_h;
+  int32_t batch;                 /* <= 65535                                                                */
+  int32_t num_heads;             /* 1..128                                                                  */
+  int32_t latent_dim;            /* 512                                                                     */
+  int32_t rope_dim;              /* 64                                                                      */
+  int32_t max_context_len;       /* columns of the grid: lengths are clamped to it                          */
+  int32_t block_seq;             /* positive multiple of 32                                                 */
+  int32_t score_mode;            /* SVK_SCORE_NONE / HEADMAX / PERHEAD                                      */
+  int32_t slot_rows;             /* rows of active_slots                                                    */
+  float softmax_scale;           /* finite, > 0                                                             */
+  int32_t _pad;
+} SvkMlaDecodeStage1Args;
+int svk_mla_decode_stage1(const SvkMlaDecodeStage1Args* a, svk_stream_t stream);
+
+/* Stage 2: output[b,h,:] = sum_j exp(lse_j - M) mid_o[b,h,j,:] / sum_j exp(lse_j - M) over the blocks
+ * j < ceil(min(context_lens[b], max_context_len) / block_seq), bf16; a lane of length 0 gets zeros.
+ * Replaces kernels/triton/mla/decode_stage2.py:19-85. */
+typedef struct SvkMlaDecodeStage2Args {
+  const float* mid_o;
+  const float* mid_lse;
+  const int32_t* context_lens;
+  uint16_t* output;              /* [B, H, 512] bf16, 8-byte aligned rows                                   */
+  int64_t mid_o_stride_b, mid_o_stride_h, mid_o_stride_s, mid_lse_stride_b, mid_lse_stride_h;
+  int64_t o_stride_b, o_stride_h;
+  int32_t batch, num_heads, latent_dim, block_seq, max_context_len, _pad;
+} SvkMlaDecodeStage2Args;
+int svk_mla_decode_stage2(const SvkMlaDecodeStage2Args* a, svk_stream_t stream);
+
+/* latent[n,:] -> latent_cache[slot_mapping[n],:], rope[n,:] -> rope_cache[slot_mapping[n],:]; a slot outside
+ * [0, num_slots) (-1 = padding) is skipped.  Replaces kernels/triton/mla/copy_latent.py:17-85. */
+typedef struct SvkMlaStoreLatentArgs {
+  const uint16_t* latent;        /* [N, 512] bf16 */
+  const uint16_t* rope;          /* [N, 64] bf16  */
+  uint16_t* latent_cache;
+  uint16_t* rope_cache;
+  const int32_t* slot_mapping;   /* [N] */
+  int64_t latent_stride, rope_stride, latent_slot_stride, rope_slot_stride;   /* elements, multiples of 8 */
+  int64_t num_slots;
+  int32_t n_tokens, latent_dim, rope_dim, _pad;
+} SvkMlaStoreLatentArgs;
+int svk_mla_store_latent(const SvkMlaStoreLatentArgs* a, svk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Quest: query-aware page top-k

@@ -23,7 +23,7 @@ SVK_SCORE_NONE = 0
 SVK_SCORE_HEADMAX = 2
 SVK_SCORE_PERHEAD = 3
 
-SVK_ABI_VERSION = 21
+SVK_ABI_VERSION = 22
 
 SVK_PREFILL_SCORE_PROBABILITY = 0
 SVK_PREFILL_SCORE_LOGITS = 1
@@ -328,6 +328,30 @@ class SvkRkvJointScoreArgs(C.Structure):
                [(n, _i32) for n in ("rows", "window", "n_candidates", "candidate_start")] + [("alpha", _f32), ("_pad", _i32)]
 
 
+class SvkMlaDecodeStage1Args(C.Structure):
+    _fields_ = [(n, _p) for n in ("q_latent", "q_rope", "latent_cache", "rope_cache", "active_slots", "request_indices",
+                                  "context_lens", "mid_o", "mid_lse", "attn_score")] + \
+               [(n, _i64) for n in ("q_latent_stride_b", "q_latent_stride_h", "q_rope_stride_b", "q_rope_stride_h",
+                                    "latent_slot_stride", "rope_slot_stride", "num_slots", "slots_stride",
+                                    "mid_o_stride_b", "mid_o_stride_h", "mid_o_stride_s", "mid_lse_stride_b",
+                                    "mid_lse_stride_h", "score_stride_b", "score_stride_h")] + \
+               [(n, _i32) for n in ("batch", "num_heads", "latent_dim", "rope_dim", "max_context_len", "block_seq",
+                                    "score_mode", "slot_rows")] + [("softmax_scale", _f32), ("_pad", _i32)]
+
+
+class SvkMlaDecodeStage2Args(C.Structure):
+    _fields_ = [(n, _p) for n in ("mid_o", "mid_lse", "context_lens", "output")] + \
+               [(n, _i64) for n in ("mid_o_stride_b", "mid_o_stride_h", "mid_o_stride_s", "mid_lse_stride_b",
+                                    "mid_lse_stride_h", "o_stride_b", "o_stride_h")] + \
+               [(n, _i32) for n in ("batch", "num_heads", "latent_dim", "block_seq", "max_context_len", "_pad")]
+
+
+class SvkMlaStoreLatentArgs(C.Structure):
+    _fields_ = [(n, _p) for n in ("latent", "rope", "latent_cache", "rope_cache", "slot_mapping")] + \
+               [(n, _i64) for n in ("latent_stride", "rope_stride", "latent_slot_stride", "rope_slot_stride", "num_slots")] + \
+               [(n, _i32) for n in ("n_tokens", "latent_dim", "rope_dim", "_pad")]
+
+
 # symbol -> (argtypes) ; every entry point declared in include/svk.h
 ENTRY_POINTS = {
     "svk_abi_version": ([], C.c_int),
@@ -355,6 +379,9 @@ ENTRY_POINTS = {
     "svk_rkv_redundancy_avg_stride": ([_i32], C.c_int64),
     "svk_rkv_redundancy": ([C.POINTER(SvkRkvRedundancyArgs), _p], C.c_int),
     "svk_rkv_joint_scores": ([C.POINTER(SvkRkvJointScoreArgs), _p], C.c_int),
+    "svk_mla_decode_stage1": ([C.POINTER(SvkMlaDecodeStage1Args), _p], C.c_int),
+    "svk_mla_decode_stage2": ([C.POINTER(SvkMlaDecodeStage2Args), _p], C.c_int),
+    "svk_mla_store_latent": ([C.POINTER(SvkMlaStoreLatentArgs), _p], C.c_int),
     "svk_deltakv_decode_alloc": ([C.POINTER(SvkDeltakvDecodeAllocArgs), _p], C.c_int),
     "svk_deltakv_device_step_begin": ([C.POINTER(SvkDeltakvDeviceStepArgs), _p], C.c_int),
     "svk_deltakv_static_decode_plan": ([C.POINTER(SvkDeltakvPlanArgs), _p], C.c_int),

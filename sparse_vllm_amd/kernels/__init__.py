@@ -5,3 +5,5 @@ from .gqa_flash_decoding_stage1 import flash_decode_stage1, flash_decode_stage1_
 from .flash_decoding_stage2 import flash_decode_stage2  # noqa: F401
 from .store_kvcache import store_kvcache  # noqa: F401
 from .rkv_ops import redundancy_scores_from_slots, select_rkv_indices_batch  # noqa: F401
+from .mla import (allocate_mla_decode_workspace, copy_latent_to_cache, decode_stage1, decode_stage2,  # noqa: F401
+                  run_mla_decode)
