@@ -40,7 +40,7 @@ typedef enum SvkStatus {
   SVK_ERR_LAUNCH = -4   /* HIP launch failure                  -> RuntimeError   */
 } SvkStatus;
 
-#define SVK_ABI_VERSION 22
+#define SVK_ABI_VERSION 23
 
 int svk_abi_version(void);
 const char* svk_last_error(void);
@@ -614,6 +614,36 @@ typedef struct SvkMlaStoreLatentArgs {
 } SvkMlaStoreLatentArgs;
 int svk_mla_store_latent(const SvkMlaStoreLatentArgs* a, svk_stream_t stream);
 
+/* Prefill gather (ABI 23): for every b < batch and j < min(context_lens[b], max_context_len), the latent and RoPE rows
+ * of slot active_slots[request_indices[b], j] are copied to packed row packed_start_locs[b] + j of the two outputs.
+ * A slot outside [0, num_slots) gives a zero row (no row is read); a request index outside [0, slot_rows) has length 0;
+ * a packed row outside [0, out_capacity) is not written.  Both cache layouts of the decode are accepted through the
+ * strides.  The packed rows feed the caller's kv_b_proj; the expanded [visible, H, 256] keys / values then go through
+ * svk_context_attention_fwd (head_dim 256) with the slot table packed_start_locs[b] + j.
+ * Replaces kernels/triton/mla/gather_latent.py:18-119 (launch :268-336). */
+typedef struct SvkMlaGatherLatentArgs {
+  const uint16_t* latent_cache;      /* bf16, 16-byte aligned                                               */
+  const uint16_t* rope_cache;        /* bf16, 16-byte aligned                                               */
+  const int32_t* active_slots;       /* [slot_rows, slots_stride]                                           */
+  const int32_t* request_indices;    /* [B]                                                                 */
+  const int32_t* context_lens;       /* [B]                                                                 */
+  const int32_t* packed_start_locs;  /* [B]                                                                 */
+  uint16_t* gathered_latent;         /* [out_capacity, 512] bf16 out, 16-byte aligned rows                  */
+  uint16_t* gathered_rope;           /* [out_capacity, 64] bf16 out, 16-byte aligned rows                   */
+  int64_t latent_slot_stride, rope_slot_stride;     /* elements between slots (>= 512 / 64, multiples of 8) */
+  int64_t num_slots;                 /* slots in the pool                                                   */
+  int64_t slots_stride;              /* >= max_context_len                                                  */
+  int64_t out_latent_stride, out_rope_stride;       /* elements between packed rows (multiples of 8)        */
+  int64_t out_capacity;              /* packed rows of the outputs (>= 0)                                   */
+  int32_t batch;                     /* <= 65535                                                            */
+  int32_t slot_rows;                 /* rows of active_slots                                                */
+  int32_t max_context_len;           /* lengths are clamped to it (>= 0)                                    */
+  int32_t latent_dim;                /* 512                                                                 */
+  int32_t rope_dim;                  /* 64                                                                  */
+  int32_t _pad;
+} SvkMlaGatherLatentArgs;
+int svk_mla_gather_latent(const SvkMlaGatherLatentArgs* a, svk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Quest: query-aware page top-k
  * ---------------------------------------------------------------------------------- */
@@ -994,7 +1024,8 @@ int svk_deltakv_materialize_sparse_view(const SvkDeltakvMaterializeArgs* a, svk_
 /* o[t, h, :] = softmax_j(q[t, h] . k[j] * D^-0.5) v[j] over the keys j <= prompt_cache_len[b] + (t - start_loc[b]) of
  * sequence b, keys / values read through req_to_tokens[b_req_idx[b], j] (the chunk's own K/V are already stored).
  * base-2 online softmax with the reference's constants (sm_scale = D^-0.5 * log2(e), masked logits = -1e8), P rounded
- * to bf16 before P.V, fp32 accumulation.
+ * to bf16 before P.V, fp32 accumulation.  head_dim 64, 128, or 256 with a GQA group of 1, 2 or 4 (ABI 23: MLA-expanded MHA
+ * and the 256-wide GQA models; 98 KiB of dynamic LDS per workgroup).
  * Replaces context_attention_fwd (attn_score=None), kernels/triton/context_flashattention_nopad.py:10-78, 242-276
  * (call sites layers/attention_backend.py:140, operators/prefill_attention.py:621-625). */
 typedef struct SvkContextAttentionArgs {

@@ -23,7 +23,7 @@ SVK_SCORE_NONE = 0
 SVK_SCORE_HEADMAX = 2
 SVK_SCORE_PERHEAD = 3
 
-SVK_ABI_VERSION = 22
+SVK_ABI_VERSION = 23
 
 SVK_PREFILL_SCORE_PROBABILITY = 0
 SVK_PREFILL_SCORE_LOGITS = 1
@@ -352,6 +352,14 @@ class SvkMlaStoreLatentArgs(C.Structure):
                [(n, _i32) for n in ("n_tokens", "latent_dim", "rope_dim", "_pad")]
 
 
+class SvkMlaGatherLatentArgs(C.Structure):
+    _fields_ = [(n, _p) for n in ("latent_cache", "rope_cache", "active_slots", "request_indices", "context_lens",
+                                  "packed_start_locs", "gathered_latent", "gathered_rope")] + \
+               [(n, _i64) for n in ("latent_slot_stride", "rope_slot_stride", "num_slots", "slots_stride",
+                                    "out_latent_stride", "out_rope_stride", "out_capacity")] + \
+               [(n, _i32) for n in ("batch", "slot_rows", "max_context_len", "latent_dim", "rope_dim", "_pad")]
+
+
 # symbol -> (argtypes) ; every entry point declared in include/svk.h
 ENTRY_POINTS = {
     "svk_abi_version": ([], C.c_int),
@@ -382,6 +390,7 @@ ENTRY_POINTS = {
     "svk_mla_decode_stage1": ([C.POINTER(SvkMlaDecodeStage1Args), _p], C.c_int),
     "svk_mla_decode_stage2": ([C.POINTER(SvkMlaDecodeStage2Args), _p], C.c_int),
     "svk_mla_store_latent": ([C.POINTER(SvkMlaStoreLatentArgs), _p], C.c_int),
+    "svk_mla_gather_latent": ([C.POINTER(SvkMlaGatherLatentArgs), _p], C.c_int),
     "svk_deltakv_decode_alloc": ([C.POINTER(SvkDeltakvDecodeAllocArgs), _p], C.c_int),
     "svk_deltakv_device_step_begin": ([C.POINTER(SvkDeltakvDeviceStepArgs), _p], C.c_int),
     "svk_deltakv_static_decode_plan": ([C.POINTER(SvkDeltakvPlanArgs), _p], C.c_int),

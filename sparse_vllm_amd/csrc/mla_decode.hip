@@ -393,6 +393,29 @@ __global__ void __launch_bounds__(256) mla_store_latent_kernel(const SvkMlaStore
         *reinterpret_cast<const uint4*>(a.rope + n * a.rope_stride + (c - 64) * 8);
 }
 
+// Prefill gather, one 16-byte chunk per thread as above: packed row packed_start_locs[b] + j <- the cache rows of slot
+// active_slots[request_indices[b], j]; a slot outside the pool gives a zero row and is never dereferenced.
+__global__ void __launch_bounds__(256) mla_gather_latent_kernel(const SvkMlaGatherLatentArgs a) {
+  const int b = blockIdx.y;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t j = idx / kMlaChunks;
+  const int c = (int)(idx % kMlaChunks);
+  const int64_t r = a.request_indices[b];
+  if (r < 0 || r >= a.slot_rows || j >= min(a.context_lens[b], a.max_context_len)) return;
+  const int64_t dst = (int64_t)a.packed_start_locs[b] + j;
+  if (dst < 0 || dst >= a.out_capacity) return;
+  const int64_t slot = a.active_slots[r * a.slots_stride + j];
+  const bool live = slot >= 0 && slot < a.num_slots;
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (c < 64) {
+    if (live) v = *reinterpret_cast<const uint4*>(a.latent_cache + slot * a.latent_slot_stride + c * 8);
+    *reinterpret_cast<uint4*>(a.gathered_latent + dst * a.out_latent_stride + c * 8) = v;
+  } else {
+    if (live) v = *reinterpret_cast<const uint4*>(a.rope_cache + slot * a.rope_slot_stride + (c - 64) * 8);
+    *reinterpret_cast<uint4*>(a.gathered_rope + dst * a.out_rope_stride + (c - 64) * 8) = v;
+  }
+}
+
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <int MODE>
@@ -503,4 +526,29 @@ extern "C" int svk_mla_store_latent(const SvkMlaStoreLatentArgs* a, svk_stream_t
   hipLaunchKernelGGL(mla_store_latent_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), *a);
   return check_launch("svk_mla_store_latent");
+}
+
+extern "C" int svk_mla_gather_latent(const SvkMlaGatherLatentArgs* a, svk_stream_t stream) {
+  using namespace svk;
+  SVK_REQUIRE(a != nullptr, SVK_ERR_VALUE, "svk_mla_gather_latent: null args");
+  SVK_REQUIRE(a->latent_dim == kMlaL && a->rope_dim == kMlaR, SVK_ERR_LAYOUT,
+              "svk_mla_gather_latent: latent_dim %d / rope_dim %d unsupported (512 / 64)", a->latent_dim, a->rope_dim);
+  SVK_REQUIRE(a->latent_cache && a->rope_cache && a->active_slots && a->request_indices && a->context_lens &&
+                  a->packed_start_locs && a->gathered_latent && a->gathered_rope,
+              SVK_ERR_VALUE, "svk_mla_gather_latent: null tensor pointer");
+  SVK_REQUIRE(a->latent_slot_stride >= kMlaL && a->latent_slot_stride % 8 == 0 && a->rope_slot_stride >= kMlaR &&
+                  a->rope_slot_stride % 8 == 0 && a->out_latent_stride >= kMlaL && a->out_latent_stride % 8 == 0 &&
+                  a->out_rope_stride >= kMlaR && a->out_rope_stride % 8 == 0 && al16(a->latent_cache) &&
+                  al16(a->rope_cache) && al16(a->gathered_latent) && al16(a->gathered_rope),
+              SVK_ERR_LAYOUT, "svk_mla_gather_latent: pointers and row strides must keep 16-byte alignment (rows >= 512 / 64)");
+  SVK_REQUIRE(a->num_slots > 0 && a->slot_rows > 0 && a->out_capacity >= 0 && a->max_context_len >= 0 &&
+                  a->slots_stride >= a->max_context_len,
+              SVK_ERR_VALUE, "svk_mla_gather_latent: empty pool / slot table, negative capacity (%lld) or max_context_len (%d), "
+              "or slots_stride %lld below max_context_len", (long long)a->out_capacity, a->max_context_len, (long long)a->slots_stride);
+  SVK_REQUIRE(a->batch >= 0 && a->batch <= 65535, SVK_ERR_VALUE, "svk_mla_gather_latent: batch %d must lie in 0..65535", a->batch);
+  if (a->batch == 0 || a->max_context_len == 0 || a->out_capacity == 0) return SVK_OK;
+  const int64_t chunks = (int64_t)a->max_context_len * kMlaChunks;
+  hipLaunchKernelGGL(mla_gather_latent_kernel, dim3((unsigned)((chunks + 255) / 256), a->batch), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), *a);
+  return check_launch("svk_mla_gather_latent");
 }

@@ -747,16 +747,22 @@ int launch_attn_scores(const SvkContextAttentionArgs& a, hipStream_t s) {
   return check_launch("svk_context_attention_fwd (scores)");
 }
 }  // namespace
+
+// head_dim 256: rows-split kernel of prefill_attention_d256.hip
+int launch_context_attention_d256(const SvkContextAttentionArgs& a, int max_input_len, bool off32, hipStream_t s);
 }  // namespace svk
 
 extern "C" int svk_context_attention_fwd(const SvkContextAttentionArgs* a, svk_stream_t stream) {
   using namespace svk;
   SVK_REQUIRE(a != nullptr, SVK_ERR_VALUE, "svk_context_attention_fwd: null args");
-  SVK_REQUIRE(a->head_dim == 64 || a->head_dim == 128, SVK_ERR_LAYOUT, "svk_context_attention_fwd: head_dim %d unsupported (64, 128)", a->head_dim);
+  SVK_REQUIRE(a->head_dim == 64 || a->head_dim == 128 || a->head_dim == 256, SVK_ERR_LAYOUT,
+              "svk_context_attention_fwd: head_dim %d unsupported (64, 128, 256)", a->head_dim);
   SVK_REQUIRE(a->num_kv_heads >= 1 && a->num_q_heads % a->num_kv_heads == 0, SVK_ERR_LAYOUT,
               "svk_context_attention_fwd: q heads %d not divisible by kv heads %d", a->num_q_heads, a->num_kv_heads);
   const int G = a->num_q_heads / a->num_kv_heads;
   SVK_REQUIRE(G >= 1 && G <= 8, SVK_ERR_LAYOUT, "svk_context_attention_fwd: GQA group size %d unsupported (1..8)", G);
+  SVK_REQUIRE(a->head_dim != 256 || G == 1 || G == 2 || G == 4, SVK_ERR_LAYOUT,
+              "svk_context_attention_fwd: head_dim 256 supports GQA group sizes 1, 2, 4, got %d", G);
   SVK_REQUIRE((a->q_stride_t % 8) == 0 && (a->q_stride_h % 8) == 0 && (a->o_stride_t % 8) == 0 && (a->o_stride_h % 8) == 0 &&
                   (a->kv_slot_stride % 8) == 0 && (a->kv_head_stride % 8) == 0,
               SVK_ERR_LAYOUT, "svk_context_attention_fwd: q/k/v/o strides must keep 16-byte alignment");
@@ -777,6 +783,12 @@ extern "C" int svk_context_attention_fwd(const SvkContextAttentionArgs* a, svk_s
   const size_t shm = (size_t)G * (kQTile * kPRowP * 2 + 256);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool off32 = a->kv_num_slots > 0 && (a->kv_num_slots * a->kv_slot_stride * 2) < (int64_t)0xffffffffll - 8192;
+  if (a->head_dim == 256) {
+    const int rc = launch_context_attention_d256(*a, a->max_input_len & kPaLenMask, off32, s);
+    if (rc != SVK_OK) return rc;
+    if (a->attn_score != nullptr) return launch_attn_scores(*a, s);
+    return SVK_OK;
+  }
   if (a->head_dim == 128) {   // LDS-shared K/V tiles; head_dim 64 keeps the first kernel (every wave fetches its own tile)
     const size_t tiles = 3 * 2 * kKV2 * kRowB, stage = (size_t)G * kQTile * 128 * 2;
     const size_t shm2 = (tiles > stage ? tiles : stage) + 2 * kKV2 * sizeof(int) + (size_t)G * 32 * sizeof(float);

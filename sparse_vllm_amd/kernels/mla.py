@@ -1,6 +1,8 @@
-"""MLA (multi-head latent attention) decode over the latent cache on device (libsvk.so): split-KV stage 1 with fused
-token scores, the LSE merge and the latent store.  Names and argument order follow the reference's
-kernels/triton/mla/{decode_stage1,decode_stage2,copy_latent,decode_schedule}.py; see include/svk.h (SvkMla*Args).
+"""MLA (multi-head latent attention) over the latent cache on device (libsvk.so): split-KV decode stage 1 with fused
+token scores, the LSE merge, the latent store, and the prefill path (ragged gather of the visible rows, the caller's
+kv_b_proj, causal attention over the expanded head_dim 256 keys / values).  Names and argument order follow the
+reference's kernels/triton/mla/{decode_stage1,decode_stage2,copy_latent,decode_schedule,gather_latent}.py and
+layers/mla_attention.py; see include/svk.h (SvkMla*Args).
 
 The cache is either the reference's two tensors (`[slots, 1, 512]`, `[slots, 1, 64]`) or two views of one interleaved
 `[slots, 576]` allocation (`buf[:, :512]`, `buf[:, 512:]`, any shape whose last dim is the row and whose first stride is
@@ -236,4 +238,100 @@ def run_mla_decode(q_latent, q_rope, latent_cache, rope_cache, active_slots, req
                   workspace.block_seq, mid_o, mid_lse, attn_score=attn_score, max_context_len=width,
                   softmax_scale=softmax_scale)
     decode_stage2(workspace.block_seq, context_lens, mid_o, mid_lse, output, max_context_len=width)
+    return output
+
+
+@torch.no_grad()
+def gather_latent_history(latent_cache, rope_cache, active_slots, request_indices, context_lens, packed_start_locs,
+                          gathered_latent, gathered_rope, *, max_context_len: int) -> None:
+    """Rows active_slots[request_indices[b], j], j < context_lens[b], of both caches to packed rows
+    packed_start_locs[b] + j of gathered_latent [capacity, 512] / gathered_rope [capacity, 64] (gather_latent.py:268-336).
+    A slot outside the pool gives a zero row; a negative request index has length 0."""
+    _check_dtypes(torch.bfloat16, latent_cache=latent_cache, rope_cache=rope_cache, gathered_latent=gathered_latent,
+                  gathered_rope=gathered_rope)
+    _check_dtypes(torch.int32, active_slots=active_slots, request_indices=request_indices, context_lens=context_lens,
+                  packed_start_locs=packed_start_locs)
+    lat_stride = _cache_rows("latent_cache", latent_cache, MLA_LATENT_DIM)
+    rope_stride = _cache_rows("rope_cache", rope_cache, MLA_ROPE_DIM)
+    if latent_cache.shape[0] != rope_cache.shape[0]:
+        raise ValueError("latent_cache and rope_cache must have equal slots")
+    if active_slots.ndim != 2 or active_slots.stride(1) != 1:
+        raise ValueError("active_slots must have shape [rows, max_context_len]")
+    if context_lens.ndim != 1 or context_lens.numel() == 0:
+        raise ValueError("context_lens must be a non-empty one-dimensional tensor")
+    batch = int(context_lens.numel())
+    for name, t in (("request_indices", request_indices), ("packed_start_locs", packed_start_locs)):
+        if tuple(t.shape) != (batch,):
+            raise ValueError(f"{name} must have shape ({batch},), got {tuple(t.shape)}")
+    if gathered_latent.ndim != 2 or gathered_latent.shape[1] != MLA_LATENT_DIM or gathered_latent.stride(1) != 1:
+        raise ValueError("gathered_latent must have shape [capacity, 512]")
+    if gathered_rope.ndim != 2 or gathered_rope.shape[1] != MLA_ROPE_DIM or gathered_rope.stride(1) != 1:
+        raise ValueError("gathered_rope must have shape [capacity, 64]")
+    if gathered_latent.shape[0] != gathered_rope.shape[0]:
+        raise ValueError("gathered_latent and gathered_rope capacities must match")
+    width = int(max_context_len)
+    if width < 0 or width > active_slots.shape[1]:
+        raise ValueError(f"max_context_len must be within active_slots capacity: {width} > {active_slots.shape[1]}")
+    lib = _lib.load()
+    a = _lib.SvkMlaGatherLatentArgs(
+        latent_cache=_lib.ptr(latent_cache), rope_cache=_lib.ptr(rope_cache), active_slots=_lib.ptr(active_slots),
+        request_indices=_lib.ptr(request_indices), context_lens=_lib.ptr(context_lens),
+        packed_start_locs=_lib.ptr(packed_start_locs), gathered_latent=_lib.ptr(gathered_latent),
+        gathered_rope=_lib.ptr(gathered_rope), latent_slot_stride=lat_stride, rope_slot_stride=rope_stride,
+        num_slots=latent_cache.shape[0], slots_stride=active_slots.stride(0), out_latent_stride=gathered_latent.stride(0),
+        out_rope_stride=gathered_rope.stride(0), out_capacity=gathered_latent.shape[0], batch=batch,
+        slot_rows=active_slots.shape[0], max_context_len=width, latent_dim=MLA_LATENT_DIM, rope_dim=MLA_ROPE_DIM)
+    _lib.check(lib.svk_mla_gather_latent(C.byref(a), _lib.current_stream_handle()), lib)
+
+
+@torch.no_grad()
+def run_mla_prefill(q, latent_cache, rope_cache, active_slots, request_indices, context_lens, b_start_loc, chunk_lens,
+                    project_latent, output, *, qk_nope_head_dim: int = 192, value_head_dim: int = 256) -> torch.Tensor:
+    """MLA chunked prefill over the explicit view (layers/mla_attention.py:374-822, 944-984): q bf16 [tokens, H, 256]
+    (192 no-position dims | 64 RoPE dims) -> output bf16 [tokens, H, 256].  The chunk's own latent / RoPE rows are
+    already in the caches; `context_lens` counts them, `chunk_lens` are the query rows per sequence and `b_start_loc`
+    their first row in q.  `project_latent` is the caller's kv_b_proj: bf16 [visible, 512] -> [visible, H * 448]
+    (per head 192 key dims | 256 value dims).  The lengths are read on the host (one synchronisation per call)."""
+    qk_head_dim = int(qk_nope_head_dim) + MLA_ROPE_DIM
+    if qk_head_dim != 256 or int(value_head_dim) != 256:
+        raise ValueError(f"MLA explicit prefill requires equal Q/K/V head widths of 256, got qk={qk_head_dim} "
+                         f"(nope {qk_nope_head_dim} + rope {MLA_ROPE_DIM}) v={value_head_dim}.")
+    if q.ndim != 3 or q.shape[2] != qk_head_dim:
+        raise ValueError(f"MLA prefill q must have shape [tokens, local_heads, 256], got {tuple(q.shape)}.")
+    if tuple(output.shape) != (q.shape[0], q.shape[1], int(value_head_dim)):
+        raise ValueError(f"output must have shape {(q.shape[0], q.shape[1], int(value_head_dim))}, got {tuple(output.shape)}")
+    _check_dtypes(torch.bfloat16, q=q, output=output)
+    _check_dtypes(torch.int32, context_lens=context_lens, b_start_loc=b_start_loc, chunk_lens=chunk_lens)
+    batch, heads, dev = int(context_lens.numel()), int(q.shape[1]), q.device
+    for name, t in (("b_start_loc", b_start_loc), ("chunk_lens", chunk_lens)):
+        if tuple(t.shape) != (batch,):
+            raise ValueError(f"{name} must have shape ({batch},), got {tuple(t.shape)}.")
+    contexts, chunks = [int(x) for x in context_lens.tolist()], [int(x) for x in chunk_lens.tolist()]
+    if any(c <= 0 or c > n for c, n in zip(chunks, contexts)):
+        raise ValueError(f"MLA prefill chunk lengths must be positive and no larger than their contexts: "
+                         f"chunks={chunks} contexts={contexts}.")
+    visible, width = sum(contexts), max(contexts)
+    # packed offsets and the slot table packed_offsets[b] + j of the explicit view
+    offsets = [0] * batch
+    for i in range(1, batch):
+        offsets[i] = offsets[i - 1] + contexts[i - 1]
+    packed_offsets = torch.tensor(offsets, dtype=torch.int32, device=dev)
+    packed_slots = packed_offsets[:, None] + torch.arange(width, dtype=torch.int32, device=dev)[None, :]
+    gathered_latent = torch.empty((visible, MLA_LATENT_DIM), dtype=torch.bfloat16, device=dev)
+    gathered_rope = torch.empty((visible, MLA_ROPE_DIM), dtype=torch.bfloat16, device=dev)
+    gather_latent_history(latent_cache, rope_cache, active_slots, request_indices, context_lens, packed_offsets,
+                          gathered_latent, gathered_rope, max_context_len=width)
+    expanded = project_latent(gathered_latent)
+    projected = int(qk_nope_head_dim) + int(value_head_dim)
+    if expanded.dtype is not torch.bfloat16 or expanded.numel() != visible * heads * projected:
+        raise RuntimeError(f"project_latent must return bf16 [{visible}, {heads} * {projected}], got "
+                           f"{expanded.dtype} {tuple(expanded.shape)}")
+    expanded = expanded.view(visible, heads, projected)
+    k = torch.empty((visible, heads, qk_head_dim), dtype=torch.bfloat16, device=dev)
+    k[..., :qk_nope_head_dim].copy_(expanded[..., :qk_nope_head_dim])
+    k[..., qk_nope_head_dim:].copy_(gathered_rope[:, None, :])
+    v = expanded[..., qk_nope_head_dim:].contiguous()
+    from .context_flashattention_nopad import context_attention_fwd
+    context_attention_fwd(q, k, v, output, torch.arange(batch, dtype=torch.int32, device=dev), b_start_loc, context_lens,
+                          context_lens - chunk_lens, max(chunks), packed_slots)
     return output
