@@ -40,7 +40,7 @@ typedef enum SvkStatus {
   SVK_ERR_LAUNCH = -4   /* HIP launch failure                  -> RuntimeError   */
 } SvkStatus;
 
-#define SVK_ABI_VERSION 23
+#define SVK_ABI_VERSION 24
 
 int svk_abi_version(void);
 const char* svk_last_error(void);
@@ -120,7 +120,12 @@ int svk_copy_slots(const SvkCopySlotsArgs* a, svk_stream_t stream);
  * mid_o = acc / sum_exp, mid_lse = max + log(sum_exp); empty blocks write (0, -inf);
  * scores are raw logits (before 1/sqrt(D)), 2-D scores are max-combined with what the
  * buffer already holds (the reference pre-fills -1e20 and uses atomic_max).
- * P is rounded to bf16 before P.V like `exp_logic.to(v.dtype)` (:280). */
+ * P is rounded to bf16 before P.V like `exp_logic.to(v.dtype)` (:280).
+ * head_dim 256 (ABI 24; struct layouts unchanged): a kernel of its own with two waves per KV head, each owning 128 head
+ * dims of both products (decode_attention_d256.hip) - same partial format, same scores, score_mode / score_overwrite /
+ * slot_page_size / the plain fused store / direct_o / kv_num_slots as at 64 and 128, GQA group 1..8, 1..8 KV heads per
+ * rank.  It refuses the ROTATED fused store (new_cos_sin != NULL) with SVK_ERR_LAYOUT: the DeltaKV view is head_dim 128
+ * only.  svk_flash_decode_stage2 merges 256-wide partials in all three of its forms. */
 typedef struct SvkFlashDecodeStage1Args {
   const uint16_t* q;             /* [B, Hq, D] bf16                                      */
   const uint16_t* k_cache;       /* [slots, Hkv, D] bf16, slot stride kv_slot_stride     */
@@ -143,7 +148,7 @@ typedef struct SvkFlashDecodeStage1Args {
   int32_t batch;
   int32_t num_q_heads;
   int32_t num_kv_heads;
-  int32_t head_dim;              /* 64 or 128                                            */
+  int32_t head_dim;              /* 64, 128 or 256                                       */
   int32_t max_len_in_batch;      /* grid covers ceil(max_len/block_seq) blocks           */
   int32_t block_seq;             /* multiple of 16                                       */
   int32_t score_mode;            /* SVK_SCORE_*                                          */

@@ -700,12 +700,16 @@ int dispatch_group(const SvkFlashDecodeStage1Args& a, int G, hipStream_t stream)
 }
 
 }  // namespace
+
+// head_dim 256: the two-waves-per-KV-head kernel of decode_attention_d256.hip
+int launch_flash_decode_stage1_d256(const SvkFlashDecodeStage1Args& a, hipStream_t stream);
 }  // namespace svk
 
 static int validate_stage1(const SvkFlashDecodeStage1Args* a, const char* who) {
   using namespace svk;
   SVK_REQUIRE(a != nullptr, SVK_ERR_VALUE, "%s: null args", who);
-  SVK_REQUIRE(a->head_dim == 64 || a->head_dim == 128, SVK_ERR_LAYOUT, "%s: head_dim %d unsupported (64, 128)", who, a->head_dim);
+  SVK_REQUIRE(a->head_dim == 64 || a->head_dim == 128 || a->head_dim == 256, SVK_ERR_LAYOUT,
+              "%s: head_dim %d unsupported (64, 128, 256)", who, a->head_dim);
   SVK_REQUIRE(a->block_seq > 0 && a->block_seq % 16 == 0, SVK_ERR_LAYOUT,
               "%s: block_seq %d must be a positive multiple of 16 (BLOCK_SEQ %% BLOCK_N)", who, a->block_seq);
   SVK_REQUIRE(a->num_kv_heads >= 1 && a->num_kv_heads <= 8, SVK_ERR_LAYOUT, "%s: num_kv_heads %d unsupported (1..8 per rank)", who,
@@ -730,6 +734,7 @@ static int validate_stage1(const SvkFlashDecodeStage1Args* a, const char* who) {
                 SVK_ERR_LAYOUT, "%s: new_k/new_v rows must be 16-byte aligned", who);
   }
   if (a->new_cos_sin != nullptr) {
+    SVK_REQUIRE(a->head_dim != 256, SVK_ERR_LAYOUT, "%s: the rotated store is head_dim 64 / 128 only, got %d", who, a->head_dim);
     SVK_REQUIRE(a->score_mode == SVK_SCORE_NONE && a->slot_page_size == 0, SVK_ERR_VALUE,
                 "%s: the rotated store rides in unscored launches over token slots only", who);
     SVK_REQUIRE(a->new_k != nullptr && a->raw_k_cache != nullptr && a->raw_v_cache != nullptr && a->new_slot_to_pos != nullptr,
@@ -755,6 +760,10 @@ extern "C" int svk_flash_decode_stage1(const SvkFlashDecodeStage1Args* a, svk_st
   if (a->batch <= 0 || a->max_len_in_batch <= 0) return SVK_OK;
   const int G = a->num_q_heads / a->num_kv_heads;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (a->head_dim == 256) {
+    if (G < 1 || G > 8) return dispatch_group<128>(*a, G, s);      // the shared "GQA group size" refusal
+    return launch_flash_decode_stage1_d256(*a, s);
+  }
   return a->head_dim == 128 ? dispatch_group<128>(*a, G, s) : dispatch_group<64>(*a, G, s);
 }
 
@@ -769,8 +778,8 @@ extern "C" int64_t svk_flash_decode_stage2_split_workspace_bytes(int32_t batch, 
 extern "C" int svk_flash_decode_stage2(const SvkFlashDecodeStage2Args* a, svk_stream_t stream) {
   using namespace svk;
   SVK_REQUIRE(a != nullptr, SVK_ERR_VALUE, "svk_flash_decode_stage2: null args");
-  SVK_REQUIRE(a->head_dim == 64 || a->head_dim == 128, SVK_ERR_LAYOUT,
-              "svk_flash_decode_stage2: head_dim %d unsupported (64, 128)", a->head_dim);
+  SVK_REQUIRE(a->head_dim == 64 || a->head_dim == 128 || a->head_dim == 256, SVK_ERR_LAYOUT,
+              "svk_flash_decode_stage2: head_dim %d unsupported (64, 128, 256)", a->head_dim);
   SVK_REQUIRE(a->block_seq > 0, SVK_ERR_VALUE, "svk_flash_decode_stage2: block_seq must be positive");
   SVK_REQUIRE(a->extra_partials >= 0 && a->extra_partials <= 8, SVK_ERR_VALUE, "svk_flash_decode_stage2: extra_partials %d out of range", a->extra_partials);
   SVK_REQUIRE((a->mid_o_stride_h % 4) == 0 && (a->mid_o_stride_s % 4) == 0 && (a->mid_o_stride_b % 4) == 0 &&
@@ -791,12 +800,17 @@ extern "C" int svk_flash_decode_stage2(const SvkFlashDecodeStage2Args* a, svk_st
     SVK_REQUIRE((reinterpret_cast<uintptr_t>(a->split_ws) % 256) == 0, SVK_ERR_LAYOUT,
                 "svk_flash_decode_stage2: split_ws must be 256-byte aligned");
     dim3 grid3(a->batch, a->num_q_heads, split_groups(a->max_partials));
-    if (a->head_dim == 128) hipLaunchKernelGGL((decode_stage2_split_kernel<128>), grid3, dim3(256), 0, s, *a);
+    if (a->head_dim == 256) hipLaunchKernelGGL((decode_stage2_split_kernel<256>), grid3, dim3(256), 0, s, *a);
+    else if (a->head_dim == 128) hipLaunchKernelGGL((decode_stage2_split_kernel<128>), grid3, dim3(256), 0, s, *a);
     else hipLaunchKernelGGL((decode_stage2_split_kernel<64>), grid3, dim3(256), 0, s, *a);
     return check_launch("svk_flash_decode_stage2");
   }
   const bool wide = (a->max_partials > 0 ? (int64_t)a->max_partials : a->mid_lse_stride_h) > 128;
-  if (a->head_dim == 128) {
+  if (a->head_dim == 256) {
+    // 64 lanes per partial row: 4 lane groups at 256 threads (8 prefetched rows each), 16 at 1024 (two-level LDS sum)
+    if (wide) hipLaunchKernelGGL((decode_stage2_kernel<256, 1024>), grid, dim3(1024), 0, s, *a);
+    else hipLaunchKernelGGL((decode_stage2_kernel<256, 256>), grid, dim3(256), 0, s, *a);
+  } else if (a->head_dim == 128) {
     if (wide) hipLaunchKernelGGL((decode_stage2_kernel<128, 1024>), grid, dim3(1024), 0, s, *a);
     else hipLaunchKernelGGL((decode_stage2_kernel<128, 256>), grid, dim3(256), 0, s, *a);
   } else {

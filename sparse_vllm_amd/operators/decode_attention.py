@@ -8,9 +8,9 @@ requires_attention_scores) -> (BLOCK_SEQ, block_n, num_warps)`, `DECODE_ATTENTIO
 `PreparedDecodeAttentionLaunchOp(spec, provider)` and `prepare_decode_attention_launch_op(spec, *, device_index=None)`.
 The reference's H100 provider is not carried over (it refuses every device but "NVIDIA H100 80GB HBM3").
 
-The MI355X provider wants two more facts than the reference's call passes — how many sequences the launch serves and how
-many KV heads a workgroup holds.  Both are OPTIONAL keyword arguments of its `launch_config`; the prepared op fills
-`num_kv_heads` from its spec and `Attention.forward` passes `batch_size` only to an op that says it takes it
+The MI355X provider wants three more facts than the reference's call passes — how many sequences the launch serves, how
+many KV heads a workgroup holds and the head dim (the head_dim 256 kernel runs two waves per KV head).  All are OPTIONAL
+keyword arguments of its `launch_config`; the prepared op fills `num_kv_heads` and `head_dim` from its spec and `Attention.forward` passes `batch_size` only to an op that says it takes it
 (`accepts_batch_size`), so a provider with the reference's three-argument `launch_config` works here unchanged.
 """
 
@@ -83,7 +83,9 @@ class Mi355xDecodeLaunchProvider(DecodeAttentionLaunchProvider):
     still owns a workgroup.  So: the largest 16-aligned BLOCK_SEQ that still yields >= one block per CU - and, for the
     1- and 2-KV-head ranks of a tensor-parallel model (a workgroup is then one or two waves), >= one wave per SIMD:
       Hq/Hkv = 7/1, B=256: 4224 -> 178.9 us (3.1 TB/s), 2112 -> 112.6, 1056 -> 97.9 (5.7 TB/s); B=64: 1056 -> 51.3, 272 -> 30.1
-      Hq/Hkv = 14/2, B=256: 4224 -> 208.2 us, 2112 -> 186.4 (6.0 TB/s)"""
+      Hq/Hkv = 14/2, B=256: 4224 -> 208.2 us, 2112 -> 186.4 (6.0 TB/s)
+    At head_dim 256 (decode_attention_d256.hip) a workgroup is 2 * Hkv waves, so the one-wave-per-SIMD floor is reached
+    with half as many workgroups; the one-workgroup-per-CU floor is unchanged."""
     name = "mi355x_hip_gqa"
     priority = 100
     RESIDENT_WORKGROUPS = 256       # one workgroup per CU
@@ -99,8 +101,8 @@ class Mi355xDecodeLaunchProvider(DecodeAttentionLaunchProvider):
             return SupportResult.no(f"requires gfx950 (MI355X), got arch {caps.arch!r} on {caps.device_name}")
         if spec.activation_dtype != torch.bfloat16:
             return SupportResult.no(f"requires BF16 query/KV tensors, got {spec.activation_dtype}")
-        if spec.head_dim not in (64, 128):
-            return SupportResult.no(f"requires head_dim 64 or 128, got {spec.head_dim}")
+        if spec.head_dim not in (64, 128, 256):
+            return SupportResult.no(f"requires head_dim 64, 128 or 256, got {spec.head_dim}")
         if not 1 <= spec.num_query_heads // spec.num_kv_heads <= 8:
             return SupportResult.no(f"requires a GQA group of 1..8 query heads per KV head, got {spec.num_query_heads}/{spec.num_kv_heads}")
         if not 1 <= spec.num_kv_heads <= 8:
@@ -110,12 +112,14 @@ class Mi355xDecodeLaunchProvider(DecodeAttentionLaunchProvider):
         return SupportResult.yes()
 
     def launch_config(self, *, block_seq: int, max_context_len: int, requires_attention_scores: bool,
-                      batch_size: int | None = None, num_kv_heads: int | None = None) -> tuple[int, int, int]:
+                      batch_size: int | None = None, num_kv_heads: int | None = None,
+                      head_dim: int | None = None) -> tuple[int, int, int]:
         del block_seq, requires_attention_scores
         b = max(1, int(batch_size or 1))
         length = max(1, int(max_context_len))
-        hkv = max(1, int(num_kv_heads or 4))                             # waves per workgroup
-        groups = max(self.RESIDENT_WORKGROUPS, -(-self.RESIDENT_WAVES // hkv))
+        hkv = max(1, int(num_kv_heads or 4))
+        waves = 2 * hkv if int(head_dim or 128) == 256 else hkv          # waves per workgroup
+        groups = max(self.RESIDENT_WORKGROUPS, -(-self.RESIDENT_WAVES // waves))
         nblk = max(1, -(-groups // b))                                   # blocks per sequence wanted
         bs = -(-length // nblk)                                          # tokens per block
         bs = max(self.MIN_BLOCK_SEQ, -(-bs // 16) * 16)
@@ -134,6 +138,7 @@ class PreparedDecodeAttentionLaunchOp:
         # optional extras a provider may declare beyond the reference's three arguments
         self.accepts_batch_size = "batch_size" in declared
         self._wants_kv_heads = "num_kv_heads" in declared
+        self._wants_head_dim = "head_dim" in declared
 
     @property
     def name(self) -> str:
@@ -142,6 +147,8 @@ class PreparedDecodeAttentionLaunchOp:
     def launch_config(self, **kwargs) -> tuple[int, int, int]:
         if self._wants_kv_heads:
             kwargs.setdefault("num_kv_heads", int(self.spec.num_kv_heads))
+        if self._wants_head_dim:
+            kwargs.setdefault("head_dim", int(self.spec.head_dim))
         return self.provider.launch_config(**kwargs)
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmark for the scored decode path (development tool, GPU only).
 
-    python tools/kbench.py [--batches 1,8,64] [--block-seqs 64,128,256] [--iters 50]
+    python tools/kbench.py [--batches 1,8,64] [--block-seqs 64,128,256] [--iters 50] [--heads 16,8 --head-dim 256]
 """
 import argparse
 import os
@@ -25,12 +25,13 @@ def main():
     ap.add_argument("--graph-pair", action="store_true", help="time stage 1 + stage 2 of one layer, back to back in a hipGraph "
                     "(small batches: eager launches are CPU-bound)")
     ap.add_argument("--heads", default="28,4", help="query heads, KV heads of the rank (7,1 = one TP=4 rank of Qwen2.5-7B)")
+    ap.add_argument("--head-dim", type=int, default=128, choices=(64, 128, 256), help="256: the two-waves-per-KV-head stage 1")
     args = ap.parse_args()
     from _warm import warm
     warm()                                  # clocks settled before the first timed configuration (tools/_warm.py)
     d = torch.device("cuda:0")
     Hq, Hkv = (int(x) for x in args.heads.split(","))
-    D, L = 128, args.len
+    D, L = args.head_dim, args.len
     torch.manual_seed(20260625)
     for B in [int(x) for x in args.batches.split(",")]:
         slots = B * L + 4096
