@@ -20,42 +20,28 @@
 //   * online softmax statistics with DPP row reductions (16 tokens live in one DPP row);
 //   * P.V on the matrix cores as well: P (rounded to bf16 like `exp_logic.to(v.dtype)`) goes through a 1.25 KiB
 //     per-wave LDS tile whose rows are the A operand, V rows are read as 16-byte segments in the B-operand token order.
+//
+// The pieces of the tile body live in decode_stage1_tile.hpp, one copy for this kernel and the head_dim 256 kernel of
+// decode_attention_d256.hip: empty-block fill, plain fused store and its fence pair, K / V addressing, slot fetch,
+// prologue, K and V tile loads, Q.K^T, score emission, online softmax, P write and rescale, P.V, the HEADMAX chunk
+// combine, the epilogue and the host-side dispatch.  The device pieces are statement macros (SVK_S1_*) over this
+// kernel's locals - the header says why and lists the names.  This file keeps v3's LDS layout, the order in which v3
+// composes the pieces, the rotated store with its early loads, and stage 2.
 
 #include <stdlib.h>
-#include <type_traits>
 
-#include "svk_common.hpp"
+#include "decode_stage1_tile.hpp"
 #include "rope_row.hpp"
 #include "svk_select.hpp"
 
 namespace svk {
 namespace {
 
-constexpr int kTileTokens = 32;    // 2 MFMA column groups of 16 tokens
-constexpr int kScoreChunk = 256;   // tokens between two score-combine barriers
-
 template <int D, int G>
 struct Stage1Cfg {
   static constexpr int NC = D / 32;          // MFMA k-chunks per head row
-  static constexpr int JQ = (G + 3) / 4;     // accumulator row groups holding real heads
-  static constexpr int PH = JQ * 4;          // padded heads per token in the P tile
-  static constexpr int DC = D / 8;           // lanes per V head row (16 B each)
-  static constexpr int TQ = 64 / DC;         // tokens per V wave-load
-  static constexpr int NV = kTileTokens / TQ;
-  static constexpr int P_FLOATS = kTileTokens * PH;
-  static constexpr int WAVE_FLOATS = P_FLOATS + 16;
+  static constexpr int JQ = stage1_jq(G);
 };
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-
-template <bool NT>
-__device__ __forceinline__ uint4 ld16(const char* p) {
-  if (NT) return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p)));
-  return *reinterpret_cast<const uint4*>(p);
-}
-
-constexpr int kPRow = 40;                          // P tile row stride in bf16 (32 tokens + pad, 16-byte aligned rows)
-constexpr int kPFloats = 16 * kPRow / 2;           // P tile [16][kPRow] bf16 expressed in floats
 
 template <int D, int G>
 struct Stage1V3Lds {
@@ -87,7 +73,6 @@ decode_stage1_kernel_v3(const SvkFlashDecodeStage1Args a) {
   const int n = lane & 15;
   const int jq = lane >> 4;
   const int dg = n % DW;                           // V: 16-byte segment (8 head dims) of this lane's MFMA column
-  constexpr int score_mode = MODE;
 
   const int len = a.b_seqlen[b];
   // rotated form of the fused store (unscored launches): what it needs and what depends on nothing but (b, w, lane) is
@@ -121,29 +106,15 @@ decode_stage1_kernel_v3(const SvkFlashDecodeStage1Args a) {
   float* spart = lds + Hkv * WF;
   const int SP = Hkv * JQ;
 
-  float* mid_o = a.mid_o + (int64_t)b * a.mid_o_stride_b + (int64_t)blk * a.mid_o_stride_s;
-  float* mid_lse = a.mid_lse + (int64_t)b * a.mid_lse_stride_b + blk;
-
-  uint16_t* direct_o = a.direct_o == nullptr ? nullptr : a.direct_o + (int64_t)b * a.direct_stride_b;
+  SVK_S1_OUT_PTRS()
   if (end <= start) {
-    for (int h = 0; h < G; ++h) {
-      if (direct_o != nullptr) {
-        for (int d = lane; d < D; d += 64) direct_o[(int64_t)(w * G + h) * a.direct_stride_h + d] = 0;
-      } else {
-        float* o = mid_o + (int64_t)(w * G + h) * a.mid_o_stride_h;
-        for (int d = lane; d < D; d += 64) o[d] = 0.f;
-      }
-      if (lane == 0) mid_lse[(int64_t)(w * G + h) * a.mid_lse_stride_h] = -INFINITY;
-    }
+    SVK_S1_FILL_EMPTY(w, D, )
     return;
   }
 
   if (a.new_k != nullptr && end == len) {
     // fused store_kvcache: this workgroup owns the lane's newest token.  Wave w writes its kv head's K and V rows
-    // (2 x D/8 lanes, 16 bytes each) before any read of the row.  Only this wave reads that slot's head row in this
-    // launch and the CU cannot hold a stale line of it (L1 is write-through, invalidated at kernel start), so a
-    // workgroup-scope fence pair (= the store has completed) is enough; agent scope would write back the XCD's L2
-    // (+10 us per launch measured).
+    // before any read of the row, in the rotated form below or the plain one.
     if (rotated) {
       if constexpr (MODE == SVK_SCORE_NONE) {
         // rotated store (include/svk.h): the raw rows go to the pre-RoPE cache, the view's row of position len-1 gets
@@ -171,84 +142,12 @@ decode_stage1_kernel_v3(const SvkFlashDecodeStage1Args a) {
           *reinterpret_cast<uint4*>(const_cast<uint16_t*>(a.v_cache) + vd + HD2) = rot_v2;
         }
       }
-    } else {
-      const int ns = a.slot_mapping[b];
-      if (ns >= 0 && lane < 2 * DW) {
-        const bool is_v = lane >= DW;
-        const int seg = lane % DW;
-        const uint16_t* src = (is_v ? a.new_v : a.new_k) + (int64_t)b * a.new_stride_b + (int64_t)w * a.new_stride_h + seg * 8;
-        uint16_t* dst = const_cast<uint16_t*>(is_v ? a.v_cache : a.k_cache) + (int64_t)ns * a.kv_slot_stride +
-                        (int64_t)w * a.kv_head_stride + seg * 8;
-        *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    } else
+      SVK_S1_STORE_NEW_KV(w, , seg * 8)
+    SVK_S1_STORE_FENCE()
   }
-  const int32_t* row = a.req_to_tokens + (int64_t)a.b_req_idx[b] * a.req_stride;
-  // Byte addressing.  OFF32: the whole K (V) tensor spans < 4 GiB, so a row address is the
-  // wave-uniform tensor base (SGPR pair) + a 32-bit per-lane byte offset: one VGPR per address
-  // and 32-bit integer math instead of 64-bit (frees ~20 VGPRs in the pipelined loop).
-  const char* const kt = reinterpret_cast<const char*>(a.k_cache);
-  const char* const vt = reinterpret_cast<const char*>(a.v_cache);
-  const int64_t slot_bytes = a.kv_slot_stride * 2;
-  const int64_t k_lane_bytes = ((int64_t)w * a.kv_head_stride + jq * 8) * 2;
-  const int64_t v_lane_bytes = ((int64_t)w * a.kv_head_stride + dg * 8) * 2;
-  auto k_ptr = [&](int slot) -> const char* {
-    if (OFF32) return kt + (size_t)((uint32_t)slot * (uint32_t)slot_bytes + (uint32_t)k_lane_bytes);
-    return kt + (int64_t)slot * slot_bytes + k_lane_bytes;
-  };
-  auto v_ptr = [&](int slot) -> const char* {
-    if (OFF32) return vt + (size_t)((uint32_t)slot * (uint32_t)slot_bytes + (uint32_t)v_lane_bytes);
-    return vt + (int64_t)slot * slot_bytes + v_lane_bytes;
-  };
-  const float sm_scale = rsqrtf((float)D);
-
-  // slot ids of one 32-token tile: lanes 0..31 fetch row[t0 + lane] (one coalesced 128 B read)
-  // (index clamped to the last valid token: always a legal, branch-free load - a conditional
-  //  load would make the compiler's vmcnt bookkeeping conservative for the whole tile body)
-  // (slot_page_size > 0, a power of two: `row` holds page slots, token slot = page slot * size + offset in the page)
-  const int page_shift = a.slot_page_size > 0 ? __builtin_ctz((unsigned)a.slot_page_size) : 0;
-  const uint32_t page_mask = (uint32_t)max(a.slot_page_size, 1) - 1u;
-  auto fetch_slots = [&](int t0) -> int {
-    const uint32_t t = (uint32_t)min(t0 + (lane_id_fresh() & 31), end - 1);
-    return (row[t >> page_shift] << page_shift) + (int)(t & page_mask);
-  };
-  auto wave_sync = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
-
-  // ---- prologue
-  for (int i = lane; i < kPFloats; i += 64) Pw[i] = 0.f;
-  {
-    const int s0 = fetch_slots(start);
-    if (lane < 32) slot_lds[lane] = s0;
-    const uint16_t* qp = a.q + (int64_t)b * a.q_stride_b + (int64_t)(w * G + n) * a.q_stride_h + jq * 8;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      uint4 t = make_uint4(0, 0, 0, 0);
-      if (n < G) t = *reinterpret_cast<const uint4*>(qp + c * 32);
-      q_lds[c * 64 + lane] = t;
-    }
-  }
-  int s_next = fetch_slots(start + kTileTokens);     // slot ids of tile 1, parked in a register
-  wave_sync();
-  uint4 kr[2][NC];
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    const char* kp = k_ptr(slot_lds[g * 16 + n]);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) kr[g][c] = ld16<false>(kp + c * 64);
-  }
-
-  float m[4], l[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) { m[r] = -INFINITY; l[r] = 0.f; }
-  f32x4_t acc[8];                                  // acc[i][r]: head jq*4+r, head dim dg*8+i
-#pragma unroll
-  for (int i = 0; i < 8; ++i) acc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  SVK_S1_ADDRESSING(w, , dg)
+  SVK_S1_PROLOGUE(w, )                             // acc[i][r]: head jq*4+r, head dim dg*8+i
 
   int c0 = start;     // first token of the current score chunk
   int buf = 0;        // slot_lds half holding the current tile's ids
@@ -264,168 +163,35 @@ decode_stage1_kernel_v3(const SvkFlashDecodeStage1Args a) {
 
     // ---- V(i) loads (slot ids from LDS)
     uint4 vr[8];                                   // vr[e] = dims dg*8.. of token jq*8+e (the k index of P.V)
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      vr[e] = ld16<NTV>(v_ptr(cur_slots[jq * 8 + e]));
+    SVK_S1_LOAD_V(NTV)
 
-    // ---- publish tile i+1's slot ids (fetched one iteration ago), fetch tile i+2's
-    {
-      const int ln = lane_id_fresh();
-      if (ln < 32) nxt_slots[ln] = s_next;
-    }
-    s_next = fetch_slots(t0 + 2 * kTileTokens);
+    SVK_S1_ADVANCE_SLOTS()
 
     // ---- S = Q K^T on K(i)
-    f32x4_t s[2];
-    {
-      bf16x8_t qa[NC];
-#pragma unroll
-      for (int c = 0; c < NC; ++c) qa[c] = __builtin_bit_cast(bf16x8_t, q_lds[c * 64 + lane]);
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        s[g] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-          s[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[c], __builtin_bit_cast(bf16x8_t, kr[g][c]), s[g], 0, 0, 0);
-      }
-    }
+    SVK_S1_QK()
     wave_sync();        // nxt_slots visible to every lane of this wave
     // ---- K registers are dead: re-arm them with K(i+1)
     if constexpr (has_next) {
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        const char* kp = k_ptr(nxt_slots[g * 16 + n]);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) kr[g][c] = ld16<false>(kp + c * 64);
-      }
+      SVK_S1_LOAD_K(nxt_slots)
     }
 
-    bool tv[2];
-    tv[0] = full || (t0 + n < end);
-    tv[1] = full || (t0 + 16 + n < end);
+    SVK_S1_TOKEN_VALID()
+    SVK_S1_EMIT_SCORES(w, )
 
-    if constexpr (score_mode == SVK_SCORE_PERHEAD) {
-#pragma unroll
-      for (int g = 0; g < 2; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int h = jq * 4 + r;
-          if (h < G && tv[g])
-            a.attn_score[(int64_t)b * a.score_stride_b + (int64_t)(w * G + h) * a.score_stride_h + t0 + g * 16 + n] = s[g][r];
-        }
-    } else if constexpr (score_mode == SVK_SCORE_HEADMAX) {
-      if (jq < JQ) {
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-          float pm = -INFINITY;
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (jq * 4 + r < G) pm = fmaxf(pm, s[g][r]);
-          spart[(t0 - c0 + g * 16 + n) * SP + w * JQ + jq] = tv[g] ? pm : -INFINITY;
-        }
-      }
-    }
-
-    float p[2][4];
-    float alpha[4];
-    bool rescale = false;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const bool hv = (jq * 4 + r < G);
-      const float x0 = (hv && tv[0]) ? s[0][r] * sm_scale : -INFINITY;
-      const float x1 = (hv && tv[1]) ? s[1][r] * sm_scale : -INFINITY;
-      const float tmax = row16_allmax(fmaxf(x0, x1));
-      const float nm = fmaxf(m[r], tmax);
-      if (hv) {
-        alpha[r] = __expf(m[r] - nm);
-        p[0][r] = __expf(x0 - nm);
-        p[1][r] = __expf(x1 - nm);
-        rescale |= (nm != m[r]);
-      } else {
-        alpha[r] = 1.f; p[0][r] = 0.f; p[1][r] = 0.f;
-      }
-      l[r] = l[r] * alpha[r] + row16_allsum(p[0][r] + p[1][r]);
-      m[r] = hv ? nm : m[r];
-    }
-
-    if (jq < JQ) {
-#pragma unroll
-      for (int g = 0; g < 2; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Pl[(jq * 4 + r) * kPRow + g * 16 + n] = (uint16_t)f32_to_bf16_bits(p[g][r]);
-    }
-    if (__any(rescale)) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[i][r] *= alpha[r];
-    }
+    SVK_S1_SOFTMAX_STEP()
+    SVK_S1_WRITE_P_RESCALE()
+    wave_sync();
+    SVK_S1_PV()                                    // B column n of MFMA i = head dim dg*8+i
     wave_sync();
 
-    // P.V on the matrix cores: A = P [head n][tokens jq*8 .. +8] (one 16-byte LDS row read), B column n of MFMA i
-    // = head dim dg*8+i, whose 8 k-values are the i-th halves of the 8 loaded 16-byte V segments.
-    {
-      const bf16x8_t pfrag = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(Pl + n * kPRow + jq * 8));
-      const uint32_t* vv = reinterpret_cast<const uint32_t*>(vr);            // vv[e * 4 + i / 2]
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        uint32_t vf[4];
-#pragma unroll
-        for (int e2 = 0; e2 < 4; ++e2)
-          vf[e2] = __builtin_amdgcn_perm(vv[(2 * e2 + 1) * 4 + i / 2], vv[(2 * e2) * 4 + i / 2], (i & 1) ? 0x07060302u : 0x05040100u);
-        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pfrag, __builtin_bit_cast(bf16x8_t, make_uint4(vf[0], vf[1], vf[2], vf[3])), acc[i], 0, 0, 0);
-      }
-    }
-    wave_sync();
-
-    // ---- end of a score chunk (or of the block): one owner thread per token column
-    if (score_mode == SVK_SCORE_HEADMAX && (!has_next || (t0 + kTileTokens - c0) == kScoreChunk)) {
-      const int c1 = min(end, t0 + kTileTokens);
-      __syncthreads();
-      float* const dst = a.attn_score + (int64_t)b * a.score_stride_b + c0;     // wave-uniform base
-      for (uint32_t t = threadIdx.x; t < (uint32_t)(c1 - c0); t += blockDim.x) {
-        float mx = -INFINITY;
-        for (int j = 0; j < SP; ++j) mx = fmaxf(mx, spart[t * SP + j]);
-        dst[t] = a.score_overwrite ? mx : fmaxf(dst[t], mx);
-      }
-      __syncthreads();
-      c0 = t0 + kTileTokens;
-    }
+    SVK_S1_SCORE_CHUNK_END(__syncthreads)
     t0 += kTileTokens;
     buf ^= 1;
   };
   while (t0 + kTileTokens < end) tile(std::true_type{});
   tile(std::false_type{});
 
-  // ---- epilogue: lane (n, jq) owns heads jq*4+r and head dims dg*8 .. +8.  The lane id is laundered through an
-  // empty asm so that none of the output addresses can be hoisted above the tile loop.
-  int lane_e = lane;
-  asm volatile("" : "+v"(lane_e));
-  const int n_e = lane_e & 15, jq_e = lane_e >> 4;
-  if (jq_e < JQ) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int h = jq_e * 4 + r;
-      if (h < G) {
-        if (n_e == 0) mid_lse[(int64_t)(w * G + h) * a.mid_lse_stride_h] = m[r] + __logf(l[r]);
-        if (n_e < DW) {
-          if (direct_o != nullptr) {
-            // the single partial of the row IS the output: stage 2 would weight it by exp(lse - lse) = 1 and round
-            uint32_t pk[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              pk[e] = f32_to_bf16_bits(acc[2 * e][r] / l[r]) | (f32_to_bf16_bits(acc[2 * e + 1][r] / l[r]) << 16);
-            *reinterpret_cast<uint4*>(direct_o + (int64_t)(w * G + h) * a.direct_stride_h + (n_e % DW) * 8) =
-                make_uint4(pk[0], pk[1], pk[2], pk[3]);
-          } else {
-            float* o = mid_o + (int64_t)(w * G + h) * a.mid_o_stride_h + (n_e % DW) * 8;
-            *reinterpret_cast<float4*>(o) = make_float4(acc[0][r] / l[r], acc[1][r] / l[r], acc[2][r] / l[r], acc[3][r] / l[r]);
-            *reinterpret_cast<float4*>(o + 4) = make_float4(acc[4][r] / l[r], acc[5][r] / l[r], acc[6][r] / l[r], acc[7][r] / l[r]);
-          }
-        }
-      }
-    }
-  }
+  SVK_S1_EPILOGUE(w, , if (n_e < DW), (n_e % DW))
 }
 
 template <int D, int THREADS>
@@ -660,43 +426,17 @@ decode_stage2_split_kernel(const SvkFlashDecodeStage2Args a) {
   }
 }
 
-template <int D, int G>
+template <int D>
 int launch_stage1(const SvkFlashDecodeStage1Args& a, hipStream_t stream) {
-  using C = Stage1Cfg<D, G>;
   const int nblk = (a.max_len_in_batch + a.block_seq - 1) / a.block_seq;
   dim3 grid(nblk, a.batch);
   dim3 block(64 * a.num_kv_heads);
-  const size_t score_floats = a.score_mode == SVK_SCORE_HEADMAX ? (size_t)kScoreChunk * a.num_kv_heads * C::JQ : 0;
-  const size_t shm3 = sizeof(float) * ((size_t)a.num_kv_heads * Stage1V3Lds<D, G>::WAVE_FLOATS + score_floats);
-  // 32-bit row offsets whenever the caller tells us the KV tensors span < 4 GiB
-  const bool off32 = a.kv_num_slots > 0 && (a.kv_num_slots * a.kv_slot_stride * 2) < (int64_t)0xffffffffll;
-#define SVK_LAUNCH_V3(MODE_)                                                                                      \
-  do {                                                                                                            \
-    if (off32) hipLaunchKernelGGL((decode_stage1_kernel_v3<D, G, MODE_, true, true>), grid, block, shm3, stream, a);  \
-    else hipLaunchKernelGGL((decode_stage1_kernel_v3<D, G, MODE_, true, false>), grid, block, shm3, stream, a);       \
-  } while (0)
-  if (a.score_mode == SVK_SCORE_HEADMAX) SVK_LAUNCH_V3(SVK_SCORE_HEADMAX);
-  else if (a.score_mode == SVK_SCORE_PERHEAD) SVK_LAUNCH_V3(SVK_SCORE_PERHEAD);
-  else SVK_LAUNCH_V3(SVK_SCORE_NONE);
-#undef SVK_LAUNCH_V3
-  return check_launch("svk_flash_decode_stage1");
-}
-
-template <int D>
-int dispatch_group(const SvkFlashDecodeStage1Args& a, int G, hipStream_t stream) {
-  switch (G) {
-    case 1: return launch_stage1<D, 1>(a, stream);
-    case 2: return launch_stage1<D, 2>(a, stream);
-    case 3: return launch_stage1<D, 3>(a, stream);
-    case 4: return launch_stage1<D, 4>(a, stream);
-    case 5: return launch_stage1<D, 5>(a, stream);
-    case 6: return launch_stage1<D, 6>(a, stream);
-    case 7: return launch_stage1<D, 7>(a, stream);
-    case 8: return launch_stage1<D, 8>(a, stream);
-    default:
-      set_error("svk_flash_decode_stage1: GQA group size %d unsupported (1..8)", G);
-      return SVK_ERR_LAYOUT;
-  }
+  return stage1_dispatch(a, [&](auto g, auto mode, auto off32) {
+    constexpr int G = decltype(g)::value;
+    const size_t shm3 = sizeof(float) * ((size_t)a.num_kv_heads * Stage1V3Lds<D, G>::WAVE_FLOATS + stage1_score_floats<G>(a));
+    hipLaunchKernelGGL((decode_stage1_kernel_v3<D, G, decltype(mode)::value, true, decltype(off32)::value>), grid, block, shm3,
+                       stream, a);
+  });
 }
 
 }  // namespace
@@ -758,13 +498,9 @@ extern "C" int svk_flash_decode_stage1(const SvkFlashDecodeStage1Args* a, svk_st
   const int rc = validate_stage1(a, "svk_flash_decode_stage1");
   if (rc != SVK_OK) return rc;
   if (a->batch <= 0 || a->max_len_in_batch <= 0) return SVK_OK;
-  const int G = a->num_q_heads / a->num_kv_heads;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (a->head_dim == 256) {
-    if (G < 1 || G > 8) return dispatch_group<128>(*a, G, s);      // the shared "GQA group size" refusal
-    return launch_flash_decode_stage1_d256(*a, s);
-  }
-  return a->head_dim == 128 ? dispatch_group<128>(*a, G, s) : dispatch_group<64>(*a, G, s);
+  if (a->head_dim == 256) return launch_flash_decode_stage1_d256(*a, s);
+  return a->head_dim == 128 ? launch_stage1<128>(*a, s) : launch_stage1<64>(*a, s);
 }
 
 extern "C" int64_t svk_flash_decode_stage2_split_workspace_bytes(int32_t batch, int32_t num_q_heads, int32_t head_dim,

@@ -21,44 +21,35 @@
 //   * every wave of a workgroup walks the same [start, end), so every barrier is under workgroup-uniform control flow:
 //     the empty-block return happens before the first barrier, the peeled last tile and the score-chunk combine depend
 //     on (start, end, t0) alone.
-//   * P.V: v3's mapping unchanged on the wave's 128 V dims (acc[8]: 8 dims x 4 heads per lane).
+//   * P.V: v3's mapping on the wave's 128 V dims (acc[8]: 8 dims x 4 heads per lane).
 //   * scores: wave 0 of each pair stores (PERHEAD) or writes its tile maxima into the LDS score chunk (HEADMAX), one
 //     owner thread per token column combines across KV heads: store or max-combine, no float atomics.
 //   * epilogue: each wave writes its 128 dims of mid_o / direct_o, wave 0 of the pair writes mid_lse.
 //   * KV heads 1..4: __launch_bounds__(512); 5..8 (up to 16 waves): a second instantiation with __launch_bounds__(1024).
 //
+// Shared with v3 (decode_stage1_tile.hpp, one copy): empty-block fill, plain fused store and its fence pair, K / V
+// addressing, slot fetch, prologue, K and V tile loads, Q.K^T, score emission, online softmax, P write and rescale, P.V,
+// the HEADMAX chunk combine, the epilogue (statement macros SVK_S1_*) and the host-side dispatch.  This kernel's own: the LDS layout, the partial-S
+// exchange, the LDS-only barrier around the combine and the LEAN schedule with its three placements of the V loads.
+//
 // Not carried over: the rotated form of the fused store (deltakv_view.hip is head_dim 128 only; refused by the caller).
 
-#include <type_traits>
-
-#include "svk_common.hpp"
+#include "decode_stage1_tile.hpp"
 
 namespace svk {
 namespace {
 
-constexpr int kTileTokens = 32;    // 2 MFMA column groups of 16 tokens
-constexpr int kScoreChunk = 256;   // tokens between two score-combine barriers
-constexpr int kPRow = 40;          // P tile row stride in bf16 (32 tokens + pad, 16-byte aligned rows)
-constexpr int kPFloats = 16 * kPRow / 2;
 constexpr int kHalf = 128;         // head dims per wave
 constexpr int kNC = kHalf / 32;    // MFMA k-chunks per half row
 constexpr int kMaxLds = 160 * 1024;
 
 template <int G>
 struct D256Lds {
-  static constexpr int JQ = (G + 3) / 4;           // accumulator row groups holding real heads
+  static constexpr int JQ = stage1_jq(G);
   static constexpr int XCH = JQ * 16 * 2 * 4;      // one exchange buffer: JQ*16 lanes x 2 column groups x 4 rows
   // P tile (bf16) | 2 x 32 slot ids | Q half-fragments (kNC x 64 lanes x 16 B) | 2 exchange buffers
   static constexpr int WAVE_FLOATS = kPFloats + 64 + kNC * 64 * 4 + 2 * XCH;
 };
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-
-template <bool NT>
-__device__ __forceinline__ uint4 ld16(const char* p) {
-  if (NT) return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p)));
-  return *reinterpret_cast<const uint4*>(p);
-}
 
 template <int G, int MODE, bool OFF32, int MAXT>
 __global__ void __launch_bounds__(MAXT)
@@ -81,7 +72,6 @@ decode_stage1_d256_kernel(const SvkFlashDecodeStage1Args a) {
   const int Hkv = a.num_kv_heads;
   const int n = lane & 15;
   const int jq = lane >> 4;
-  constexpr int score_mode = MODE;
 
   const int len = a.b_seqlen[b];
   const int start = blk * a.block_seq;
@@ -97,102 +87,22 @@ decode_stage1_d256_kernel(const SvkFlashDecodeStage1Args a) {
   float* spart = lds + 2 * Hkv * WF;
   const int SP = Hkv * JQ;
 
-  float* mid_o = a.mid_o + (int64_t)b * a.mid_o_stride_b + (int64_t)blk * a.mid_o_stride_s + hx * kHalf;
-  float* mid_lse = a.mid_lse + (int64_t)b * a.mid_lse_stride_b + blk;
-  uint16_t* direct_o = a.direct_o == nullptr ? nullptr : a.direct_o + (int64_t)b * a.direct_stride_b + hx * kHalf;
+  SVK_S1_OUT_PTRS(+ hx * kHalf)
 
   // (b, blk) are the workgroup's: every wave takes this return or none does, and no barrier has been passed yet
   if (end <= start) {
-    for (int h = 0; h < G; ++h) {
-      if (direct_o != nullptr) {
-        for (int d = lane; d < kHalf; d += 64) direct_o[(int64_t)(kvh * G + h) * a.direct_stride_h + d] = 0;
-      } else {
-        float* o = mid_o + (int64_t)(kvh * G + h) * a.mid_o_stride_h;
-        for (int d = lane; d < kHalf; d += 64) o[d] = 0.f;
-      }
-      if (hx == 0 && lane == 0) mid_lse[(int64_t)(kvh * G + h) * a.mid_lse_stride_h] = -INFINITY;
-    }
+    SVK_S1_FILL_EMPTY(kvh, kHalf, hx == 0 &&)
     return;
   }
 
   if (a.new_k != nullptr && end == len) {
-    // fused store_kvcache: this workgroup owns the lane's newest token.  Wave (kvh, hx) writes ITS half of the head's K
-    // and V rows (2 x 16 lanes, 16 bytes each) before any read of the row; only this wave reads those bytes in this
-    // launch, so the workgroup-scope fence pair of v3 (= the store has completed) is enough here as well.
-    const int ns = a.slot_mapping[b];
-    if (ns >= 0 && lane < 2 * DW) {
-      const bool is_v = lane >= DW;
-      const int seg = lane % DW;
-      const int64_t col = hx * kHalf + seg * 8;
-      const uint16_t* src = (is_v ? a.new_v : a.new_k) + (int64_t)b * a.new_stride_b + (int64_t)kvh * a.new_stride_h + col;
-      uint16_t* dst = const_cast<uint16_t*>(is_v ? a.v_cache : a.k_cache) + (int64_t)ns * a.kv_slot_stride +
-                      (int64_t)kvh * a.kv_head_stride + col;
-      *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    // fused store_kvcache: wave (kvh, hx) writes ITS half of the head's K and V rows; only this wave reads those
+    // bytes in this launch, so the workgroup-scope fence pair is enough here as well
+    SVK_S1_STORE_NEW_KV(kvh, const int64_t col = hx * kHalf + seg * 8;, col)
+    SVK_S1_STORE_FENCE()
   }
-  const int32_t* row = a.req_to_tokens + (int64_t)a.b_req_idx[b] * a.req_stride;
-  // byte addressing; OFF32: wave-uniform tensor base + a 32-bit per-lane offset (the tensors span < 4 GiB)
-  const char* const kt = reinterpret_cast<const char*>(a.k_cache);
-  const char* const vt = reinterpret_cast<const char*>(a.v_cache);
-  const int64_t slot_bytes = a.kv_slot_stride * 2;
-  const int64_t k_lane_bytes = ((int64_t)kvh * a.kv_head_stride + hx * kHalf + jq * 8) * 2;
-  const int64_t v_lane_bytes = ((int64_t)kvh * a.kv_head_stride + hx * kHalf + n * 8) * 2;
-  auto k_ptr = [&](int slot) -> const char* {
-    if (OFF32) return kt + (size_t)((uint32_t)slot * (uint32_t)slot_bytes + (uint32_t)k_lane_bytes);
-    return kt + (int64_t)slot * slot_bytes + k_lane_bytes;
-  };
-  auto v_ptr = [&](int slot) -> const char* {
-    if (OFF32) return vt + (size_t)((uint32_t)slot * (uint32_t)slot_bytes + (uint32_t)v_lane_bytes);
-    return vt + (int64_t)slot * slot_bytes + v_lane_bytes;
-  };
-  const float sm_scale = rsqrtf((float)D);
-
-  // slot ids of one 32-token tile (index clamped to the last valid token: always a legal, branch-free load)
-  const int page_shift = a.slot_page_size > 0 ? __builtin_ctz((unsigned)a.slot_page_size) : 0;
-  const uint32_t page_mask = (uint32_t)max(a.slot_page_size, 1) - 1u;
-  auto fetch_slots = [&](int t0) -> int {
-    const uint32_t t = (uint32_t)min(t0 + (lane_id_fresh() & 31), end - 1);
-    return (row[t >> page_shift] << page_shift) + (int)(t & page_mask);
-  };
-  auto wave_sync = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
-  // workgroup barrier over LDS traffic only: the wave's LDS writes have completed, global loads stay in flight
-  auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-
-  // ---- prologue
-  for (int i = lane; i < kPFloats; i += 64) Pw[i] = 0.f;
-  {
-    const int s0 = fetch_slots(start);
-    if (lane < 32) slot_lds[lane] = s0;
-    const uint16_t* qp = a.q + (int64_t)b * a.q_stride_b + (int64_t)(kvh * G + n) * a.q_stride_h + hx * kHalf + jq * 8;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      uint4 t = make_uint4(0, 0, 0, 0);
-      if (n < G) t = *reinterpret_cast<const uint4*>(qp + c * 32);
-      q_lds[c * 64 + lane] = t;
-    }
-  }
-  int s_next = fetch_slots(start + kTileTokens);     // slot ids of tile 1, parked in a register
-  wave_sync();
-  uint4 kr[2][NC];
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    const char* kp = k_ptr(slot_lds[g * 16 + n]);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) kr[g][c] = ld16<false>(kp + c * 64);
-  }
-
-  float m[4], l[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) { m[r] = -INFINITY; l[r] = 0.f; }
-  f32x4_t acc[8];                                  // acc[i][r]: head jq*4+r, head dim hx*128 + n*8 + i
-#pragma unroll
-  for (int i = 0; i < 8; ++i) acc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  SVK_S1_ADDRESSING(kvh, hx * kHalf +, n)         // 16 V segments per half row = the 16 MFMA columns
+  SVK_S1_PROLOGUE(kvh, hx * kHalf +)               // acc[i][r]: head jq*4+r, head dim hx*128 + n*8 + i
 
   int c0 = start;     // first token of the current score chunk
   int buf = 0;        // parity of the tile: slot_lds half and exchange buffer in use
@@ -207,32 +117,13 @@ decode_stage1_d256_kernel(const SvkFlashDecodeStage1Args a) {
     // ---- V(i) loads: this wave's 128 dims
     uint4 vr[8];                                   // vr[e] = dims hx*128 + n*8.. of token jq*8+e (the k index of P.V)
     if constexpr (!LEAN) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        vr[e] = ld16<true>(v_ptr(cur_slots[jq * 8 + e]));
+      SVK_S1_LOAD_V(true)
     }
 
-    // ---- publish tile i+1's slot ids (fetched one iteration ago), fetch tile i+2's
-    {
-      const int ln = lane_id_fresh();
-      if (ln < 32) nxt_slots[ln] = s_next;
-    }
-    s_next = fetch_slots(t0 + 2 * kTileTokens);
+    SVK_S1_ADVANCE_SLOTS()
 
     // ---- partial S = Q[:, half] K[:, half]^T on K(i)
-    f32x4_t s[2];
-    {
-      bf16x8_t qa[NC];
-#pragma unroll
-      for (int c = 0; c < NC; ++c) qa[c] = __builtin_bit_cast(bf16x8_t, q_lds[c * 64 + lane]);
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        s[g] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-          s[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[c], __builtin_bit_cast(bf16x8_t, kr[g][c]), s[g], 0, 0, 0);
-      }
-    }
+    SVK_S1_QK()
     // ---- hand the partial tile to the partner wave (row groups holding real heads only)
     if (jq < JQ) {
 #pragma unroll
@@ -241,18 +132,11 @@ decode_stage1_d256_kernel(const SvkFlashDecodeStage1Args a) {
     lds_barrier();      // the pair's partials and this wave's nxt_slots are visible
     // ---- K registers are dead: re-arm them with K(i+1)
     if constexpr (has_next && !LEAN) {
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        const char* kp = k_ptr(nxt_slots[g * 16 + n]);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) kr[g][c] = ld16<false>(kp + c * 64);
-      }
+      SVK_S1_LOAD_K(nxt_slots)
     }
     // (per-head scores: their 64-bit store addresses and 32 V registers do not fit together - V(i) follows the stores)
-    if constexpr (LEAN && score_mode != SVK_SCORE_PERHEAD) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        vr[e] = ld16<true>(v_ptr(cur_slots[jq * 8 + e]));
+    if constexpr (LEAN && MODE != SVK_SCORE_PERHEAD) {
+      SVK_S1_LOAD_V(true)
     }
     // ---- S = half 0 + half 1, in that order in both waves
     if (jq < JQ) {
@@ -265,203 +149,58 @@ decode_stage1_d256_kernel(const SvkFlashDecodeStage1Args a) {
       }
     }
 
-    bool tv[2];
-    tv[0] = full || (t0 + n < end);
-    tv[1] = full || (t0 + 16 + n < end);
+    SVK_S1_TOKEN_VALID()
 
-    if constexpr (score_mode == SVK_SCORE_PERHEAD) {
-      if (hx == 0) {
-#pragma unroll
-        for (int g = 0; g < 2; ++g)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int h = jq * 4 + r;
-            if (h < G && tv[g])
-              a.attn_score[(int64_t)b * a.score_stride_b + (int64_t)(kvh * G + h) * a.score_stride_h + t0 + g * 16 + n] = s[g][r];
-          }
-      }
-    } else if constexpr (score_mode == SVK_SCORE_HEADMAX) {
-      if (hx == 0 && jq < JQ) {
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-          float pm = -INFINITY;
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (jq * 4 + r < G) pm = fmaxf(pm, s[g][r]);
-          spart[(t0 - c0 + g * 16 + n) * SP + kvh * JQ + jq] = tv[g] ? pm : -INFINITY;
-        }
-      }
-    }
-    if constexpr (LEAN && score_mode == SVK_SCORE_PERHEAD) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        vr[e] = ld16<true>(v_ptr(cur_slots[jq * 8 + e]));
+    SVK_S1_EMIT_SCORES(kvh, hx == 0 &&)
+    if constexpr (LEAN && MODE == SVK_SCORE_PERHEAD) {
+      SVK_S1_LOAD_V(true)
     }
 
-    float p[2][4];
-    float alpha[4];
-    bool rescale = false;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const bool hv = (jq * 4 + r < G);
-      const float x0 = (hv && tv[0]) ? s[0][r] * sm_scale : -INFINITY;
-      const float x1 = (hv && tv[1]) ? s[1][r] * sm_scale : -INFINITY;
-      const float tmax = row16_allmax(fmaxf(x0, x1));
-      const float nm = fmaxf(m[r], tmax);
-      if (hv) {
-        alpha[r] = __expf(m[r] - nm);
-        p[0][r] = __expf(x0 - nm);
-        p[1][r] = __expf(x1 - nm);
-        rescale |= (nm != m[r]);
-      } else {
-        alpha[r] = 1.f; p[0][r] = 0.f; p[1][r] = 0.f;
-      }
-      l[r] = l[r] * alpha[r] + row16_allsum(p[0][r] + p[1][r]);
-      m[r] = hv ? nm : m[r];
-    }
-
-    if (jq < JQ) {
-#pragma unroll
-      for (int g = 0; g < 2; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Pl[(jq * 4 + r) * kPRow + g * 16 + n] = (uint16_t)f32_to_bf16_bits(p[g][r]);
-    }
-    if (__any(rescale)) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[i][r] *= alpha[r];
-    }
+    SVK_S1_SOFTMAX_STEP()
+    SVK_S1_WRITE_P_RESCALE()
     wave_sync();
-
-    // P.V on the matrix cores, v3's mapping: A = P [head n][tokens jq*8 .. +8], B column n of MFMA i = head dim
-    // hx*128 + n*8 + i, whose 8 k-values are the i-th halves of the 8 loaded 16-byte V segments.
-    {
-      const bf16x8_t pfrag = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(Pl + n * kPRow + jq * 8));
-      const uint32_t* vv = reinterpret_cast<const uint32_t*>(vr);            // vv[e * 4 + i / 2]
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        uint32_t vf[4];
-#pragma unroll
-        for (int e2 = 0; e2 < 4; ++e2)
-          vf[e2] = __builtin_amdgcn_perm(vv[(2 * e2 + 1) * 4 + i / 2], vv[(2 * e2) * 4 + i / 2], (i & 1) ? 0x07060302u : 0x05040100u);
-        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pfrag, __builtin_bit_cast(bf16x8_t, make_uint4(vf[0], vf[1], vf[2], vf[3])), acc[i], 0, 0, 0);
-      }
-    }
+    SVK_S1_PV()                                    // B column n of MFMA i = head dim hx*128 + n*8 + i
     wave_sync();
     if constexpr (has_next && LEAN) {
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        const char* kp = k_ptr(nxt_slots[g * 16 + n]);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) kr[g][c] = ld16<false>(kp + c * 64);
-      }
+      SVK_S1_LOAD_K(nxt_slots)
     }
 
-    // ---- end of a score chunk (or of the block): one owner thread per token column.  The condition depends on
-    // (t0, c0, has_next) alone, which every wave of the workgroup shares.
-    if (score_mode == SVK_SCORE_HEADMAX && (!has_next || (t0 + kTileTokens - c0) == kScoreChunk)) {
-      const int c1 = min(end, t0 + kTileTokens);
-      lds_barrier();
-      float* const dst = a.attn_score + (int64_t)b * a.score_stride_b + c0;     // wave-uniform base
-      for (uint32_t t = threadIdx.x; t < (uint32_t)(c1 - c0); t += blockDim.x) {
-        float mx = -INFINITY;
-        for (int j = 0; j < SP; ++j) mx = fmaxf(mx, spart[t * SP + j]);
-        dst[t] = a.score_overwrite ? mx : fmaxf(dst[t], mx);
-      }
-      lds_barrier();
-      c0 = t0 + kTileTokens;
-    }
+    // every wave of the workgroup reaches the combine's barriers or none does: LDS-only, the loads stay in flight
+    SVK_S1_SCORE_CHUNK_END(lds_barrier)
     t0 += kTileTokens;
     buf ^= 1;
   };
   while (t0 + kTileTokens < end) tile(std::true_type{});
   tile(std::false_type{});
 
-  // ---- epilogue: lane (n, jq) owns heads jq*4+r and head dims hx*128 + n*8 .. +8 (lane id laundered as in v3)
-  int lane_e = lane;
-  asm volatile("" : "+v"(lane_e));
-  const int n_e = lane_e & 15, jq_e = lane_e >> 4;
-  if (jq_e < JQ) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int h = jq_e * 4 + r;
-      if (h < G) {
-        if (hx == 0 && n_e == 0) mid_lse[(int64_t)(kvh * G + h) * a.mid_lse_stride_h] = m[r] + __logf(l[r]);
-        if (direct_o != nullptr) {
-          // the single partial of the row IS the output: stage 2 would weight it by exp(lse - lse) = 1 and round
-          uint32_t pk[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            pk[e] = f32_to_bf16_bits(acc[2 * e][r] / l[r]) | (f32_to_bf16_bits(acc[2 * e + 1][r] / l[r]) << 16);
-          *reinterpret_cast<uint4*>(direct_o + (int64_t)(kvh * G + h) * a.direct_stride_h + n_e * 8) =
-              make_uint4(pk[0], pk[1], pk[2], pk[3]);
-        } else {
-          float* o = mid_o + (int64_t)(kvh * G + h) * a.mid_o_stride_h + n_e * 8;
-          *reinterpret_cast<float4*>(o) = make_float4(acc[0][r] / l[r], acc[1][r] / l[r], acc[2][r] / l[r], acc[3][r] / l[r]);
-          *reinterpret_cast<float4*>(o + 4) = make_float4(acc[4][r] / l[r], acc[5][r] / l[r], acc[6][r] / l[r], acc[7][r] / l[r]);
-        }
-      }
-    }
-  }
+  SVK_S1_EPILOGUE(kvh, hx == 0 &&, , n_e)
 }
 
-template <int G, int MAXT>
+// 1..4 KV heads: MAXT = 512; 5..8: 1024
+template <int MAXT>
 int launch_d256(const SvkFlashDecodeStage1Args& a, hipStream_t stream) {
-  constexpr int JQ = D256Lds<G>::JQ;
   const int nblk = (a.max_len_in_batch + a.block_seq - 1) / a.block_seq;
   dim3 grid(nblk, a.batch);
   dim3 block(128 * a.num_kv_heads);                  // two waves per KV head
-  const size_t score_floats = a.score_mode == SVK_SCORE_HEADMAX ? (size_t)kScoreChunk * a.num_kv_heads * JQ : 0;
-  const size_t shm = sizeof(float) * ((size_t)2 * a.num_kv_heads * D256Lds<G>::WAVE_FLOATS + score_floats);
-  const bool off32 = a.kv_num_slots > 0 && (a.kv_num_slots * a.kv_slot_stride * 2) < (int64_t)0xffffffffll;
-  // 5..8 KV heads (and 4 with head-max scores) need more than the 64 KiB of dynamic LDS a kernel may use by default
-#define SVK_LAUNCH_D256(MODE_, OFF32_)                                                                                  \
-  do {                                                                                                                  \
-    auto kern = decode_stage1_d256_kernel<G, MODE_, OFF32_, MAXT>;                                                      \
-    static bool wide_lds = false;                                                                                       \
-    if (shm > 64 * 1024 && !wide_lds) {                                                                                 \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds); \
-      wide_lds = true;                                                                                                  \
-    }                                                                                                                   \
-    hipLaunchKernelGGL(kern, grid, block, shm, stream, a);                                                              \
-  } while (0)
-#define SVK_LAUNCH_D256_MODE(MODE_)             \
-  do {                                          \
-    if (off32) SVK_LAUNCH_D256(MODE_, true);    \
-    else SVK_LAUNCH_D256(MODE_, false);         \
-  } while (0)
-  if (a.score_mode == SVK_SCORE_HEADMAX) SVK_LAUNCH_D256_MODE(SVK_SCORE_HEADMAX);
-  else if (a.score_mode == SVK_SCORE_PERHEAD) SVK_LAUNCH_D256_MODE(SVK_SCORE_PERHEAD);
-  else SVK_LAUNCH_D256_MODE(SVK_SCORE_NONE);
-#undef SVK_LAUNCH_D256_MODE
-#undef SVK_LAUNCH_D256
-  return check_launch("svk_flash_decode_stage1");
-}
-
-template <int MAXT>
-int dispatch_group_d256(const SvkFlashDecodeStage1Args& a, int G, hipStream_t stream) {
-  switch (G) {
-    case 1: return launch_d256<1, MAXT>(a, stream);
-    case 2: return launch_d256<2, MAXT>(a, stream);
-    case 3: return launch_d256<3, MAXT>(a, stream);
-    case 4: return launch_d256<4, MAXT>(a, stream);
-    case 5: return launch_d256<5, MAXT>(a, stream);
-    case 6: return launch_d256<6, MAXT>(a, stream);
-    case 7: return launch_d256<7, MAXT>(a, stream);
-    case 8: return launch_d256<8, MAXT>(a, stream);
-    default:
-      set_error("svk_flash_decode_stage1: GQA group size %d unsupported (1..8)", G);
-      return SVK_ERR_LAYOUT;
-  }
+  return stage1_dispatch(a, [&](auto g, auto mode, auto off32) {
+    constexpr int G = decltype(g)::value;
+    const size_t shm = sizeof(float) * ((size_t)2 * a.num_kv_heads * D256Lds<G>::WAVE_FLOATS + stage1_score_floats<G>(a));
+    auto kern = decode_stage1_d256_kernel<G, decltype(mode)::value, decltype(off32)::value, MAXT>;
+    // 5..8 KV heads (and 4 with head-max scores) need more than the 64 KiB of dynamic LDS a kernel may use by default
+    static bool wide_lds = false;                    // one per instantiation
+    if (shm > 64 * 1024 && !wide_lds) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
+      wide_lds = true;
+    }
+    hipLaunchKernelGGL(kern, grid, block, shm, stream, a);
+  });
 }
 
 }  // namespace
 
 // validated by svk_flash_decode_stage1 (decode_attention.hip): head_dim 256, 1..8 KV heads, no rotated store
 int launch_flash_decode_stage1_d256(const SvkFlashDecodeStage1Args& a, hipStream_t stream) {
-  const int G = a.num_q_heads / a.num_kv_heads;
-  return a.num_kv_heads <= 4 ? dispatch_group_d256<512>(a, G, stream) : dispatch_group_d256<1024>(a, G, stream);
+  return a.num_kv_heads <= 4 ? launch_d256<512>(a, stream) : launch_d256<1024>(a, stream);
 }
 
 }  // namespace svk

@@ -52,14 +52,6 @@ namespace {
 //   flow with per-token loads.
 // ------------------------------------------------------------------------------------------------
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
-  const f32x2_t v = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));      // v_cvt_pk_bf16_f32 (RNE)
-}
-
 template <int N>
 __device__ __forceinline__ float cvt_ubyte(uint32_t x) {
   float f;

@@ -39,15 +39,8 @@ constexpr int kMlaShm = 2 * kMlaTile + kMlaXchg + 4 * 32 * 4;
 
 typedef __attribute__((ext_vector_type(4))) short mla_s16x4_t;
 typedef __attribute__((ext_vector_type(8))) short mla_s16x8_t;
-typedef __attribute__((ext_vector_type(2))) float mla_f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 mla_bf16x2_t;
 
 __device__ uint4 mla_zero_row[kMlaChunks];            // source of masked / padding rows (zero-initialised)
-
-__device__ __forceinline__ uint32_t mla_pack_bf16(float lo, float hi) {
-  const mla_f32x2_t v = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, mla_bf16x2_t));      // v_cvt_pk_bf16_f32 (RNE)
-}
 
 // LDS position (16-byte units inside the row) of chunk c of tile row r; an involution in c, so it also maps a position
 // back to the chunk stored there.  Row r starts at bank-chunk 8 (r & 1) (1152 B = 4.5 x 256 B).  Latent chunks: the low
@@ -57,15 +50,6 @@ __device__ __forceinline__ uint32_t mla_pack_bf16(float lo, float hi) {
 __device__ __forceinline__ int mla_pos(int r, int c) {
   const int f = (((r & 3) << 2) | ((r >> 2) & 3)) ^ ((r & 1) << 3);
   return c < 64 ? ((c & ~15) | ((c ^ f) & 15)) : (64 | ((c ^ (r >> 1)) & 7));
-}
-
-// workgroup barrier that waits for this wave's LDS traffic only (the DMA of the next tile stays in flight)
-__device__ __forceinline__ void mla_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ void mla_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 template <int MODE>
@@ -223,7 +207,7 @@ __global__ void __launch_bounds__(256) mla_stage1_kernel(const SvkMlaDecodeStage
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) xch[(w * 16 + r) * 64 + lane] = s[r];
-      mla_lds_barrier();
+      lds_barrier();
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         s[r] = add_rn(add_rn(add_rn(xch[r * 64 + lane], xch[(16 + r) * 64 + lane]), xch[(32 + r) * 64 + lane]),
@@ -279,13 +263,13 @@ __global__ void __launch_bounds__(256) mla_stage1_kernel(const SvkMlaDecodeStage
       for (int r = 0; r < 16; ++r) {
         s[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], sc, -nms));
         psum += s[r];
-        if (r & 1) pp[r >> 1] = mla_pack_bf16(s[r - 1], s[r]);
+        if (r & 1) pp[r >> 1] = pack_bf16(s[r - 1], s[r]);
       }
       l_part = l_part * al + psum;
       if (k > 0 && __any(al != 1.0f)) {
         // rescale factors: "lane = head" -> "register = head" through the wave's LDS row
         if (half == 0) fac[lq] = al;
-        mla_wave_sync();
+        wave_sync();
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
           const float4 f4 = *reinterpret_cast<const float4*>(fac + 8 * jj + 4 * half);
@@ -294,7 +278,7 @@ __global__ void __launch_bounds__(256) mla_stage1_kernel(const SvkMlaDecodeStage
             o[i][4 * jj + 0] *= f4.x; o[i][4 * jj + 1] *= f4.y; o[i][4 * jj + 2] *= f4.z; o[i][4 * jj + 3] *= f4.w;
           }
         }
-        mla_wave_sync();
+        wave_sync();
       }
 
       // ---- O += P V: A = P (k index e of half <-> token 16 sp + 8 (e>>2) + 4 half + (e&3)), B = V by transposed reads
@@ -324,7 +308,7 @@ __global__ void __launch_bounds__(256) mla_stage1_kernel(const SvkMlaDecodeStage
     if (half == 0) fac[lq] = l;
     if (half == 0 && hok)
       ml[(int64_t)h * a.mid_lse_stride_h] = l > 0.f ? m_run * a.softmax_scale + logf(l) : -INFINITY;
-    mla_wave_sync();
+    wave_sync();
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
       const float4 f4 = *reinterpret_cast<const float4*>(fac + 8 * jj + 4 * half);
@@ -339,7 +323,7 @@ __global__ void __launch_bounds__(256) mla_stage1_kernel(const SvkMlaDecodeStage
         }
       }
     }
-    mla_wave_sync();
+    wave_sync();
   }
 }
 

@@ -24,13 +24,6 @@ constexpr int kQTile = 32;      // query tokens per wave
 constexpr int kKTile = 32;      // keys per iteration
 constexpr int kPRowP = 40;      // P tile row stride (bf16), 16-byte aligned rows
 
-typedef __attribute__((ext_vector_type(2))) __bf16 pa_bf16x2_t;
-typedef __attribute__((ext_vector_type(2))) float pa_f32x2_t;
-__device__ __forceinline__ uint32_t pack_bf16_pair(float lo, float hi) {
-  const pa_f32x2_t v = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, pa_bf16x2_t));      // v_cvt_pk_bf16_f32 (RNE)
-}
-
 template <int D, bool OFF32>
 __global__ void __launch_bounds__(512) context_attention_kernel(const SvkContextAttentionArgs a) {
   constexpr int NC = D / 32, DW = D / 8;
@@ -89,11 +82,6 @@ __global__ void __launch_bounds__(512) context_attention_kernel(const SvkContext
     return reinterpret_cast<const uint16_t*>(vt + (int64_t)slot * slot_bytes + v_lane_bytes);
   };
   uint32_t* Pl32 = reinterpret_cast<uint32_t*>(Pl);
-  auto wave_sync = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
   // slot ids of one key tile: lanes 0..31 read row[k0 + lane], clamped to the last visible key (always a legal row)
   auto fetch_slots = [&](int k0) -> int { return row[min(k0 + (lane & 31), kv_end - 1)]; };
   // The k index j of the second product maps to key column (j & 1) * 16 + (j >> 1), so the two probabilities a lane
@@ -174,7 +162,7 @@ __global__ void __launch_bounds__(512) context_attention_kernel(const SvkContext
         alpha[t][r] = al;
         l[t][r] = l[t][r] * al + (p0 + p1);               // lane-partial row sum: reduced across the 16 columns once, in the epilogue
         m[t][r] = nm;
-        Pl32[(t * 16 + kc * 4 + r) * (kPRowP / 2) + n] = pack_bf16_pair(p0, p1);
+        Pl32[(t * 16 + kc * 4 + r) * (kPRowP / 2) + n] = pack_bf16(p0, p1);
       }
     if (__any(rescale)) {
 #pragma unroll
@@ -546,7 +534,7 @@ __global__ void __launch_bounds__(512) context_attention_kernel_v2(const SvkCont
         }
         s_in[g] = __builtin_amdgcn_exp2f(__builtin_fmaf(s_in[g], sm_scale, -nms));
         psum += s_in[g];
-        if (g & 1) p_out[g >> 1] = pack_bf16_pair(s_in[g - 1], s_in[g]);
+        if (g & 1) p_out[g >> 1] = pack_bf16(s_in[g - 1], s_in[g]);
         __builtin_amdgcn_sched_barrier(0);
       }
     }

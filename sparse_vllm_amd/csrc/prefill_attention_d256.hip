@@ -41,16 +41,9 @@ constexpr int kIds0 = 2 * kRing * kBlkB;       // 3 pairs x 64 slot ids | 4 x 32
 constexpr int kShm = kIds0 + 3 * 64 * 4 + 4 * 32 * 4;
 constexpr int kWgRows = 128;
 
-typedef __attribute__((ext_vector_type(2))) __bf16 d2_bf16x2_t;
-typedef __attribute__((ext_vector_type(2))) float d2_f32x2_t;
 typedef __attribute__((ext_vector_type(4))) short d2_s16x4_t;
 typedef __attribute__((ext_vector_type(8))) short d2_s16x8_t;
 typedef __attribute__((address_space(3))) unsigned char lds_byte_t;
-
-__device__ __forceinline__ uint32_t pack_bf16_pair(float lo, float hi) {
-  const d2_f32x2_t v = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, d2_bf16x2_t));      // v_cvt_pk_bf16_f32 (RNE)
-}
 
 template <bool OFF32>
 __global__ void __launch_bounds__(256) context_attention_kernel_d256(const SvkContextAttentionArgs a) {
@@ -259,7 +252,7 @@ __global__ void __launch_bounds__(256) context_attention_kernel_d256(const SvkCo
         }
         s_in[g] = __builtin_amdgcn_exp2f(__builtin_fmaf(s_in[g], sm_scale, -nms));
         psum += s_in[g];
-        if (g & 1) p_out[g >> 1] = pack_bf16_pair(s_in[g - 1], s_in[g]);
+        if (g & 1) p_out[g >> 1] = pack_bf16(s_in[g - 1], s_in[g]);
         __builtin_amdgcn_sched_barrier(0);
       }
     }

@@ -32,6 +32,8 @@ constexpr int kWave = 64;
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 
 __device__ __forceinline__ float bf16_lo(uint32_t w) { return __builtin_bit_cast(float, w << 16); }
 __device__ __forceinline__ float bf16_hi(uint32_t w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
@@ -45,6 +47,20 @@ __device__ __forceinline__ uint32_t f32_to_bf16_bits(float f) {
 __device__ __forceinline__ float bf16_round(float f) {
   return __builtin_bit_cast(float, f32_to_bf16_bits(f) << 16);
 }
+// two floats -> one word of two bf16 (lo in the low half), round-to-nearest-even
+__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
+  const f32x2_t v = {lo, hi};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));      // v_cvt_pk_bf16_f32 (RNE)
+}
+
+// the wave's LDS writes are visible to all of its lanes
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// workgroup barrier that waits for this wave's LDS traffic only: global loads and LDS-DMA stay in flight
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // x*y rounded on its own (never contracted into an fma with a following add): ROCm's __fmul_rn is a
 // plain `x * y` and still fuses under -ffp-contract=fast, so the contraction is switched off locally.
