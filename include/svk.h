@@ -442,7 +442,9 @@ int svk_decode_alloc_slots(const SvkDecodeAllocArgs* a, svk_stream_t stream);
  *   logits:      max_{p,h} q_{p,h}.k_t (raw), others -inf
  * The whole [n_ranges, score_cols] buffer is overwritten (fill + scores), like the reference wrapper.
  * Replaces kernels/triton/prefill_score.py: prefill_score_fwd :432-670 (kernels :70-429),
- * PrefillScoreWorkspace :6-67.  Q.K^T runs on the matrix cores (v_mfma_f32_16x16x32_bf16). */
+ * PrefillScoreWorkspace :6-67.  Q.K^T runs on the matrix cores (v_mfma_f32_16x16x32_bf16).  head_dim 64, 128 or 256
+ * (256: MLA-expanded MHA and the 256-wide GQA models; GQA groups <= 8 with windows <= 128 take the rows-split LDS-tile
+ * kernel of prefill_score_d256.hip, 70 KiB of dynamic LDS per workgroup). */
 typedef struct SvkPrefillScoreArgs {
   const uint16_t* q;                  /* [tokens, Hq, D] bf16 (this step's chunk queries)          */
   const uint16_t* k_cache;            /* [slots, Hkv, D] bf16                                      */
@@ -469,7 +471,7 @@ typedef struct SvkPrefillScoreArgs {
   /* MI355X: softmax statistics of the window's query rows that svk_context_attention_fwd of the same chunk left behind
    * (`score_row_stats` there): probability mode then runs its final pass only - Q.K^T once instead of twice, one launch
    * instead of three; attn_score must have been cleared (`score_clear` there).  Only when every causal key is a
-   * candidate (candidate_start = 0, num_recent_tokens = 0: H2O), range i <-> sequence i, head_dim 128.  NULL = compute
+   * candidate (candidate_start = 0, num_recent_tokens = 0: H2O), range i <-> sequence i, head_dim 128 or 256.  NULL = compute
    * the statistics here (the reference's three-launch form). */
   const float* row_stats;
 } SvkPrefillScoreArgs;
@@ -1046,7 +1048,7 @@ typedef struct SvkContextAttentionArgs {
   int64_t q_stride_t, q_stride_h, kv_slot_stride, kv_head_stride, o_stride_t, o_stride_h, req_stride;
   int32_t batch, num_q_heads, num_kv_heads, head_dim, max_input_len;
   int64_t kv_num_slots;          /* slots in k_cache / v_cache (0 = unknown): < 4 GiB tensors get 32-bit row offsets */
-  /* MI355X, optional (NULL = off; head_dim 128 kernel only): the attention already owns what prefill_score_fwd's first
+  /* MI355X, optional (NULL = off; head_dim 128 and 256 kernels): the attention already owns what prefill_score_fwd's first
    * two launches compute - the final softmax statistics of every query row - so the rows of a score window
    * [score_q_start[b], b_seq_len[b]) leave them behind for svk_prefill_score(row_stats=...):
    *   score_row_stats[((b * Hkv + kvh) * G + g) * score_wpad + (pos - score_q_start[b])] = m * D^-0.5 * log2 e + log2 l

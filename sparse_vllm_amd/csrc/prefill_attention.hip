@@ -763,8 +763,8 @@ extern "C" int svk_context_attention_fwd(const SvkContextAttentionArgs* a, svk_s
     SVK_REQUIRE(a->num_q_heads <= 64 && a->num_kv_heads <= 8 && a->head_dim <= 256 && a->head_dim % 4 == 0, SVK_ERR_LAYOUT,
                 "svk_context_attention_fwd: score collection supports <= 64 query heads, <= 8 KV heads");
   }
-  SVK_REQUIRE((a->score_row_stats == nullptr && a->score_clear == nullptr) || a->head_dim == 128, SVK_ERR_LAYOUT,
-              "svk_context_attention_fwd: score statistics are produced by the head_dim 128 kernel only");
+  SVK_REQUIRE((a->score_row_stats == nullptr && a->score_clear == nullptr) || a->head_dim == 128 || a->head_dim == 256, SVK_ERR_LAYOUT,
+              "svk_context_attention_fwd: score statistics are produced by the head_dim 128 and 256 kernels only");
   SVK_REQUIRE(a->score_row_stats == nullptr || (a->score_q_start != nullptr && a->score_wpad > 0), SVK_ERR_VALUE,
               "svk_context_attention_fwd: score_row_stats needs score_q_start and score_wpad");
   dim3 grid(((a->max_input_len & kPaLenMask) + kQTile - 1) / kQTile, a->num_kv_heads, a->batch), block(64 * G);

@@ -45,7 +45,9 @@ typedef __attribute__((ext_vector_type(4))) short d2_s16x4_t;
 typedef __attribute__((ext_vector_type(8))) short d2_s16x8_t;
 typedef __attribute__((address_space(3))) unsigned char lds_byte_t;
 
-template <bool OFF32>
+// STATS: the score window's rows also leave their softmax statistics behind and the step-score rows are zeroed (svk.h:
+// score_row_stats / score_clear); the instantiation without it is the kernel as it was.
+template <bool OFF32, bool STATS>
 __global__ void __launch_bounds__(256) context_attention_kernel_d256(const SvkContextAttentionArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = threadIdx.x & 63;
@@ -316,6 +318,21 @@ __global__ void __launch_bounds__(256) context_attention_kernel_d256(const SvkCo
   __syncthreads();                                       // (the epilogue stages through the K/V rings)
   // ---- epilogue: row sums across the two halves, 1/l into register-row layout, outputs through LDS as whole rows
   l_part += lane_xor32(l_part);
+  if constexpr (STATS) {
+    if (a.score_row_stats != nullptr && half == 0) {
+      // the base-2 exponent constant of the row, m * c + log2 l, for the token-score pass.  With lazy rescaling m_run is
+      // a reference point, not the row maximum: the sum is the same number for any reference point.
+      const int qs = a.score_q_start[b];
+      const int r = pc + qtok - qs;
+      if (qs >= 0 && r >= 0 && r < a.score_wpad && qtok < q_len)
+        a.score_row_stats[((int64_t)b * a.num_q_heads + head) * a.score_wpad + r] = m_run * sm_scale + __builtin_amdgcn_logf(l_part);
+    }
+    if (a.score_clear != nullptr && kvh == 0 && m0 + q_tile >= q_len) {
+      // one workgroup per sequence (the tile that holds the chunk's last rows, KV head 0) zeroes the sequence's score row
+      float* dst = a.score_clear + (int64_t)b * a.score_clear_stride;
+      for (int c = threadIdx.x; c < a.score_clear_cols; c += 256) dst[c] = 0.f;
+    }
+  }
   if (half == 0) fac[lq] = 1.0f / l_part;
   uint16_t* ost = reinterpret_cast<uint16_t*>(lds_raw + (size_t)w * (kBlk * kRowB));       // [32 rows][256] bf16 per wave
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -353,11 +370,15 @@ __global__ void __launch_bounds__(256) context_attention_kernel_d256(const SvkCo
 // Launch of the head_dim 256 kernel for svk_context_attention_fwd (arguments already validated; G in {1, 2, 4}).
 int launch_context_attention_d256(const SvkContextAttentionArgs& a, int max_input_len, bool off32, hipStream_t s) {
   static const hipError_t attr = [] {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(context_attention_kernel_d256<true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, kShm);
-    return e != hipSuccess ? e
-                           : hipFuncSetAttribute(reinterpret_cast<const void*>(context_attention_kernel_d256<false>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kShm);
+    const void* const kernels[4] = {reinterpret_cast<const void*>(context_attention_kernel_d256<true, false>),
+                                    reinterpret_cast<const void*>(context_attention_kernel_d256<false, false>),
+                                    reinterpret_cast<const void*>(context_attention_kernel_d256<true, true>),
+                                    reinterpret_cast<const void*>(context_attention_kernel_d256<false, true>)};
+    for (const void* k : kernels) {
+      const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kShm);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
   }();
   if (attr != hipSuccess) {
     set_error("svk_context_attention_fwd: cannot reserve %d bytes of LDS per workgroup: %s", kShm, hipGetErrorString(attr));
@@ -366,8 +387,14 @@ int launch_context_attention_d256(const SvkContextAttentionArgs& a, int max_inpu
   const int G = a.num_q_heads / a.num_kv_heads;
   const int q_tile = kWgRows / G;
   const dim3 grid((max_input_len + q_tile - 1) / q_tile, a.num_kv_heads, a.batch);
-  if (off32) hipLaunchKernelGGL((context_attention_kernel_d256<true>), grid, dim3(256), (size_t)kShm, s, a);
-  else hipLaunchKernelGGL((context_attention_kernel_d256<false>), grid, dim3(256), (size_t)kShm, s, a);
+  const bool stats = a.score_row_stats != nullptr || a.score_clear != nullptr;
+  if (stats) {
+    if (off32) hipLaunchKernelGGL((context_attention_kernel_d256<true, true>), grid, dim3(256), (size_t)kShm, s, a);
+    else hipLaunchKernelGGL((context_attention_kernel_d256<false, true>), grid, dim3(256), (size_t)kShm, s, a);
+  } else {
+    if (off32) hipLaunchKernelGGL((context_attention_kernel_d256<true, false>), grid, dim3(256), (size_t)kShm, s, a);
+    else hipLaunchKernelGGL((context_attention_kernel_d256<false, false>), grid, dim3(256), (size_t)kShm, s, a);
+  }
   return check_launch("svk_context_attention_fwd (head_dim 256)");
 }
 

@@ -14,42 +14,15 @@
 
 #include <algorithm>
 
-#include "svk_common.hpp"
-#include "lds_dma.hpp"
+#include <stdlib.h>
+
+#include "prefill_score_common.hpp"
 
 namespace svk {
 namespace {
 
 constexpr int kRowsPerWg = 256;
 constexpr int kKeysPerWg = 256;
-constexpr float kMasked = -1.0e20f;
-
-__device__ __forceinline__ void atomic_max_nonneg(float* p, float v) {
-  atomicMax(reinterpret_cast<int*>(p), __builtin_bit_cast(int, v));      // valid for v >= 0, *p >= 0
-}
-__device__ __forceinline__ void atomic_max_any(float* p, float v) {
-  if (v >= 0.f) atomicMax(reinterpret_cast<int*>(p), __builtin_bit_cast(int, v));
-  else atomicMin(reinterpret_cast<unsigned int*>(p), __builtin_bit_cast(unsigned int, v));
-}
-
-struct RangeInfo {
-  int start_loc, cache_len, ctx_len, chunk_len, q_start, q_end, cand_end;
-  const int32_t* row;
-};
-
-__device__ __forceinline__ RangeInfo load_range(const SvkPrefillScoreArgs& a, int i) {
-  RangeInfo r;
-  const int s = a.batch_indices ? a.batch_indices[i] : i;
-  r.start_loc = a.b_start_loc[s];
-  r.cache_len = a.b_prompt_cache_len[s];
-  r.ctx_len = a.b_seq_len[s];
-  r.chunk_len = r.ctx_len - r.cache_len;
-  r.q_start = a.score_q_start[i];
-  r.q_end = a.score_q_end[i];
-  r.cand_end = min(max(a.candidate_start, r.ctx_len - a.num_recent_tokens), a.score_cols);
-  r.row = a.req_to_tokens + (int64_t)a.b_req_idx[s] * a.req_stride;
-  return r;
-}
 
 // PASS: 0 = partial stats, 1 = final probabilities, 2 = logits
 template <int D, int PASS>
@@ -244,13 +217,7 @@ __global__ void __launch_bounds__(256) prefill_score_kernel(const SvkPrefillScor
 //         the per-key accumulator is a register, no shuffles; one multiply-add, one exp2, one multiply-add per logit.
 //   * statistics travel between the passes in the base-2 domain (u = s D^-1/2 log2 e) and as 1 / l.
 // ------------------------------------------------------------------------------------------------
-constexpr int kPsKeys = 128;
 constexpr int kPsRowB = 256;
-
-__device__ __forceinline__ float ps_max16(const f32x16_t& x) {
-  return vmax(vmax3(vmax3(x[0], x[1], x[2]), vmax3(x[3], x[4], x[5]), x[15]),
-              vmax3(vmax3(x[6], x[7], x[8]), vmax3(x[9], x[10], x[11]), vmax3(x[12], x[13], x[14])));
-}
 
 template <int PASS>
 __global__ void __launch_bounds__(512, 4) prefill_score_kernel_v2(const SvkPrefillScoreArgs a, int G, int Wpad32, int q_limit, int NKB,
@@ -562,6 +529,11 @@ inline Tiling2 make_tiling2(const Tiling& t, int n_ranges, int Hkv, int cols) {
   return u;
 }
 }  // namespace
+
+// head_dim 256: one pass of the rows-split kernel of prefill_score_d256.hip (pass 0 statistics, 1 final, 2 logits); the
+// tiling, the partial-statistics layout and the reduce between passes 0 and 1 are v2's
+int launch_prefill_score_d256(const SvkPrefillScoreArgs& a, int pass, int G, int Wpad32, int q_limit, int NKB, float* part_m,
+                              float* part_l, const float* glob_ml, hipStream_t s);
 }  // namespace svk
 
 extern "C" int32_t svk_prefill_score_window_pad(int32_t num_q_heads, int32_t num_kv_heads, int32_t max_query_len) {
@@ -587,7 +559,8 @@ extern "C" int svk_prefill_score(const SvkPrefillScoreArgs* a, svk_stream_t stre
   SVK_REQUIRE(a != nullptr, SVK_ERR_VALUE, "svk_prefill_score: null args");
   SVK_REQUIRE(a->score_mode == SVK_PREFILL_SCORE_PROBABILITY || a->score_mode == SVK_PREFILL_SCORE_LOGITS, SVK_ERR_VALUE,
               "prefill score_mode must be 'probability' or 'logits', got %d.", a->score_mode);
-  SVK_REQUIRE(a->head_dim == 64 || a->head_dim == 128, SVK_ERR_LAYOUT, "svk_prefill_score: head_dim %d unsupported (64, 128)", a->head_dim);
+  SVK_REQUIRE(a->head_dim == 64 || a->head_dim == 128 || a->head_dim == 256, SVK_ERR_LAYOUT,
+              "svk_prefill_score: head_dim %d unsupported (64, 128, 256)", a->head_dim);
   SVK_REQUIRE(a->num_kv_heads > 0 && a->num_q_heads % a->num_kv_heads == 0, SVK_ERR_VALUE,
               "num query heads must be divisible by num kv heads: q=%d k=%d", a->num_q_heads, a->num_kv_heads);
   if (a->max_query_len <= 0 || a->score_cols <= 0 || a->n_ranges <= 0) return SVK_OK;
@@ -600,13 +573,17 @@ extern "C" int svk_prefill_score(const SvkPrefillScoreArgs* a, svk_stream_t stre
   const Tiling t = make_tiling(a->n_ranges, a->num_q_heads, a->num_kv_heads, a->max_query_len, a->score_cols, a->score_mode);
   const bool logits = a->score_mode == SVK_PREFILL_SCORE_LOGITS;
   const bool v2 = a->head_dim == 128 && t.G <= 8 && t.Wpad <= 128;
+  // head_dim 256: the rows-split LDS-tile kernel; SVK_PREFILL_SCORE_VARIANT=1 keeps the generic kernel (A/B baseline)
+  static const bool generic256 = [] { const char* e = getenv("SVK_PREFILL_SCORE_VARIANT"); return e != nullptr && atoi(e) == 1; }();
+  const bool d256 = a->head_dim == 256 && t.G <= 8 && t.Wpad <= 128 && !generic256;
   if (a->row_stats != nullptr) {
-    SVK_REQUIRE(!logits && v2, SVK_ERR_LAYOUT, "svk_prefill_score: row_stats serve the head_dim 128 probability kernel only");
+    SVK_REQUIRE(!logits && (v2 || d256), SVK_ERR_LAYOUT,
+                "svk_prefill_score: row_stats serve the head_dim 128 / 256 LDS-tile probability kernels only");
     SVK_REQUIRE(a->candidate_start == 0 && a->num_recent_tokens == 0 && a->batch_indices == nullptr, SVK_ERR_VALUE,
                 "svk_prefill_score: row_stats are the attention's statistics over ALL causal keys: candidate_start = 0, "
                 "num_recent_tokens = 0 and range i <-> sequence i are required");
   }
-  if (logits || !v2)      // (the v2 probability path clears the row inside its first pass)
+  if (logits || !(v2 || d256))      // (the v2 / head_dim 256 probability paths clear the row inside their first pass)
     hipLaunchKernelGGL(fill_rows_kernel, dim3(std::min(64, (a->score_cols + 255) / 256), a->n_ranges), dim3(256), 0, s,
                        a->attn_score, a->score_stride, a->score_cols, logits ? -INFINITY : 0.f);
   if (v2) {
@@ -634,6 +611,23 @@ extern "C" int svk_prefill_score(const SvkPrefillScoreArgs* a, svk_stream_t stre
     }
     return check_launch("svk_prefill_score");
   }
+  if (d256) {
+    const Tiling2 u = make_tiling2(t, a->n_ranges, a->num_kv_heads, a->score_cols);
+    auto pass = [&](int p, float* pm2, float* pl2, const float* gm2) {
+      return launch_prefill_score_d256(*a, p, t.G, u.Wpad32, t.q_limit, u.NKB, pm2, pl2, gm2, s);
+    };
+    if (logits) return pass(2, nullptr, nullptr, nullptr);
+    if (a->row_stats != nullptr) return pass(1, nullptr, nullptr, a->row_stats);
+    const int64_t part2 = u.groups * u.NKB * u.ROWS;
+    float* pm2 = a->workspace;
+    float* pl2 = pm2 + part2;
+    float* gm2 = pl2 + part2;
+    const int rc = pass(0, pm2, pl2, nullptr);
+    if (rc != SVK_OK) return rc;
+    hipLaunchKernelGGL(prefill_score_reduce_kernel_v2, dim3((u.ROWS + 31) / 32, (unsigned)u.groups), dim3(256), 0, s, pm2, pl2,
+                       gm2, u.NKB, u.ROWS);
+    return pass(1, nullptr, nullptr, gm2);
+  }
   dim3 grid(t.NKB, (unsigned)t.groups), block(256);
   const int64_t part = t.groups * t.NKB * kRowsPerWg, glob = t.groups * kRowsPerWg;
   float* pm = a->workspace;
@@ -654,7 +648,7 @@ extern "C" int svk_prefill_score(const SvkPrefillScoreArgs* a, svk_stream_t stre
                          nullptr, gmx, glx);                                                                               \
     }                                                                                                                      \
   } while (0)
-  if (a->head_dim == 128) SVK_PS(128); else SVK_PS(64);
+  if (a->head_dim == 256) SVK_PS(256); else if (a->head_dim == 128) SVK_PS(128); else SVK_PS(64);
 #undef SVK_PS
   return check_launch("svk_prefill_score");
 }

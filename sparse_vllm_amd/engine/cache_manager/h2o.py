@@ -257,7 +257,7 @@ class H2OCacheManager(SnapKVCacheManager):
         if enabled is None:
             import os
             enabled = self._prefill_fuse_enabled = (
-                self.config.sparse_prefill_score_mode == "probability" and self.head_dim == 128
+                self.config.sparse_prefill_score_mode == "probability" and self.head_dim in (128, 256)
                 and self.num_heads // self.num_kv_heads <= 8 and os.environ.get("SVK_PREFILL_SCORE_FUSE", "1") == "1")
             self._prefill_wpad = {}
         if not enabled or seqs is None:
